@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Benchmark of the SVD denoising hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N ...
 
 A "step" is one full rollout of the hot loop: 25 Euler steps (prep_unet_input -> UNet forward ->
@@ -16,9 +16,15 @@ per GPU — `--gpus 8 --batch 8` is BASELINE config 3, 64 candidates sharded 8 p
 the request at C candidates whatever N is (strong scaling, reported as "scaling": "strong").  Both collectives are
 inside the timed region; there is no exchange inside the loop.
 
-Extra objects on the JSON line: "roofline" for the dominant kernel (HIP-event timing of every GEMM
-launch inside the timed region, on the launch stream) and "cpu_baseline" (the CPU oracle timed on the
-host cores on a bounded sample, rank 0 / N=1 only).
+A plain run sets up, warms up, times the K steps and prints one JSON line (`metric`, `value`, `unit`,
+`higher_is_better`, `dtype`, `ms_per_step`, ...).  `--dump-outputs DIR` also writes the latents of the last
+timed rollout as DIR/latents.npy (float32; inputs and weights are seeded, so two builds compare output for output).
+
+`--full` adds everything the headline figure does not need: "box" (calibration launches of this GPU before the
+timed region), per-launch HIP events on every --event-every-th Euler step of the timed region with the
+"roofline" of the dominant kernel and the per-family rows, "power" (rocm-smi sampled over the timed region),
+"extra" (B = 8, fp16 and fp16 + fp32-stream rollouts, one whole request, training steps) and "cpu_baseline"
+(the CPU oracle timed on the host cores on a bounded sample, rank 0 / N=1 only).
 """
 import argparse
 import gc
@@ -38,6 +44,7 @@ import torch  # noqa: E402
 ALGO_TFLOP_PER_FORWARD = 89.604  # per UNet forward per candidate (CFG on), 576x1024x14 (reference graph)
 ELIDED_TFLOP_PER_FORWARD = 3.44   # single-key cross-attentions evaluated in closed form: never credited
 PEAK_BF16_TFLOPS = 2500.0        # MI355X dense bf16 MFMA (MI355X_MICROARCH.md)
+DUMP_BUDGET_BYTES = 60_000_000   # --dump-outputs: all arrays together stay below 64 MB
 MODE_NAMES = {0: "gemm_kernel<dense>", 1: "gemm_kernel<conv3x3>", 2: "gemm_kernel<conv3x3_s2>",
               3: "gemm_kernel<conv3x3_up>", 4: "gemm_kernel<conv_t3>"}
 
@@ -62,6 +69,22 @@ MODE_TEMPLATES = {
 def synth_actions(B, T):
     base = [4] + [[1, 2, 1, 3][i % 4] for i in range(T - 1)]  # exercises both rolls
     return np.tile(np.array(base, dtype=np.int64), (B, 1))
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: every array as DIR/<name>.npy in float32 (float64 stays float64).  An array larger than what is left of
+    DUMP_BUDGET_BYTES is replaced by a fixed sample of its flattened elements (RandomState(0), sorted indices), saved as
+    DIR/<name>_sample.npy."""
+    os.makedirs(dirname, exist_ok=True)
+    left = DUMP_BUDGET_BYTES
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        a = a.astype(np.float64 if a.dtype == np.float64 else np.float32, copy=False)
+        if a.nbytes > left:
+            idx = np.sort(np.random.RandomState(0).choice(a.size, left // a.itemsize, replace=False))
+            a, name = a.reshape(-1)[idx], name + "_sample"
+        np.save(os.path.join(dirname, name + ".npy"), a)
+        left -= a.nbytes
 
 
 def _cpu_model() -> str:
@@ -190,23 +213,30 @@ def main():
     ap.add_argument("--residual-fp32", action="store_true",
                     help="UNetHIP(residual_fp32=True): the residual stream in fp32 (with --dtype fp16 the configuration within "
                          "1e-3 of the reference's fp32 evaluation, DESIGN.md 5)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: box calibration, per-launch kernel events with "
+                         "the roofline and per-family rows, power sampling, the `extra` legs and the CPU baseline (off: a plain "
+                         "run sets up, warms up, times the steps and prints the line)")
+    ap.add_argument("--dump-outputs", type=str, default="", metavar="DIR",
+                    help="after the timed steps, write the latents of the last timed rollout as DIR/latents.npy (float32; "
+                         "--train: the loss of the last step as DIR/loss.npy, float64)")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the `extra` legs the default single-GPU line appends after its timed region (B = 8 rollout = "
+                    help="--full: skip the `extra` legs the single-GPU line appends after its timed region (B = 8 rollout = "
                          "BASELINE config 2's per-GPU work, fp16 and fp16 + fp32-residual rollouts, a --train leg of 2 warm-up + 5 timed steps)")
     ap.add_argument("--no-calibrate", action="store_true",
-                    help="skip the box calibration launches (rocprofv3 runs: ~100 ms of calibration kernels would lead the "
+                    help="--full: skip the box calibration launches (rocprofv3 runs: ~100 ms of calibration kernels would lead the "
                          "kernel statistics); `box` and `roofline.frac_of_box_peak` are then absent")
     ap.add_argument("--tiny", action="store_true", help="reduced-width model (plumbing check only; INVALID as a result)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-power", action="store_true", help="do not sample rocm-smi (clock, watts) during the timed region")
-    ap.add_argument("--no-kernel-events", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: no CPU baseline")
+    ap.add_argument("--no-power", action="store_true", help="--full: do not sample rocm-smi (clock, watts) during the timed region")
+    ap.add_argument("--no-kernel-events", action="store_true", help="--full: no per-launch HIP events in the timed region")
     ap.add_argument("--no-graph", action="store_true",
                     help="issue every UNet forward launch by launch (default: replay a captured hipGraph on the Euler steps "
                          "that carry no per-launch events; same bytes)")
     ap.add_argument("--event-every", type=int, default=5,
-                    help="per-launch HIP events are recorded on every n-th Euler step of the timed rollouts (every launch of "
+                    help="--full: per-launch HIP events are recorded on every n-th Euler step of the timed rollouts (every launch of "
                          "those steps); n = 1 instruments every step and costs 3.4 %% of frames/s (21 k extra events / rollout)")
-    ap.add_argument("--dump-shapes", type=str, default="", help="write per-(M,N,K) GEMM timings to this file")
+    ap.add_argument("--dump-shapes", type=str, default="", help="--full: write per-(M,N,K) GEMM timings to this file")
     ap.add_argument("--train", action="store_true",
                     help="BASELINE config 4 instead of the inference loop: one fine-tuning step per 'step' (un-fused training "
                          "forward, EDM loss, backward through every operator, AdamW), one sample per GPU, data parallel over "
@@ -220,6 +250,8 @@ def main():
                     help="also time whole requests (uint8 panorama in -> uint8 frames out: CLIP + VAE encode, denoise, VAE "
                          "decode, PIL post-processing) through server.worker.SVDWorker; reported as 'end_to_end'")
     args = ap.parse_args()
+    if args.dump_shapes and not args.full:
+        ap.error("--dump-shapes needs --full (the per-launch events it is made of)")
 
     t_start = time.perf_counter()
     rank = int(os.environ.get("RANK", "0"))
@@ -263,9 +295,9 @@ def main():
     unet = UNetHIP(cfg, sd, device, dtype=torch.float16 if args.dtype == "fp16" else torch.bfloat16,
                    residual_fp32="full" if args.residual_fp32_full else (True if args.residual_fp32 else None))
     # what THIS box gives a pure-MFMA loop and a device copy (outside the timed region): the pool's boxes differ by +-5 %
-    box = unet.hip.calibrate_box() if rank == 0 and not args.no_calibrate else None
+    box = unet.hip.calibrate_box() if args.full and rank == 0 and not args.no_calibrate else None
     sd_cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not args.tiny:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and not args.tiny:
         sd_cpu = {k: v.cpu() for k, v in sd.items()}
     del sd
     torch.cuda.empty_cache()
@@ -319,10 +351,10 @@ def main():
 
     for _ in range(args.warmup):
         rollout()
-    ev["on"] = not args.no_kernel_events
+    ev["on"] = args.full and not args.no_kernel_events
     den.host_launch = {"eager": [0.0, 0], "graph": [0.0, 0]}
     barrier()
-    pws = PowerSampler() if rank == 0 and not args.no_power else None
+    pws = PowerSampler() if args.full and rank == 0 and not args.no_power else None
     if pws is not None:
         pws.start()
     t0 = time.perf_counter()
@@ -335,6 +367,8 @@ def main():
     if dist_on:
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
     dt = float(tt.item())
+    if args.dump_outputs and rank == 0:      # before anything else runs on the denoiser's (graph-static) buffers
+        dump_outputs(args.dump_outputs, {"latents": out.float().cpu().numpy()})
 
     prof, kprof = ev["gemm"], ev["kern"]
     unet.hip.gemm_profile = None
@@ -475,7 +509,7 @@ def main():
                         f.write(f"family={k} " + " ".join(f"{a}={b}" for a, b in v.items()) + "\n")
         if args.end_to_end and world == 1 and not args.tiny:
             res["end_to_end"] = end_to_end(den, unet, device, B, args)
-        if (world == 1 and not dist_on and not args.no_extras and not args.tiny and B == 1 and not strong and
+        if (args.full and world == 1 and not dist_on and not args.no_extras and not args.tiny and B == 1 and not strong and
                 (args.height, args.width, args.num_inference_steps) == (576, 1024, 25) and not (args.residual_fp32 or args.residual_fp32_full)):
             res["extra"] = extras(args, cfg, unet, device, req, time.perf_counter() - t_start)
         if sd_cpu is not None:
@@ -551,6 +585,8 @@ def train_bench(args, rank, world, device, dist_on=False):
     line = None
     if rank == 0:
         assert np.isfinite(loss)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"loss": np.array([loss], dtype=np.float64)})
         line = ({
             "metric": "fine-tuning samples/sec (train_svd.py step: fwd + bwd + AdamW)", "value": round(world * args.steps / dt, 4),
             "unit": "samples/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -640,7 +676,7 @@ def extras(args, cfg, unet, device, req, elapsed):
     try:
         if left() > 45:
             a2 = copy.copy(args)
-            a2.steps, a2.warmup, a2.no_autotune = 5, 2, True
+            a2.steps, a2.warmup, a2.no_autotune, a2.dump_outputs = 5, 2, True, ""
             gc.collect()
             torch.cuda.empty_cache()           # four legs have churned the allocator: start the step from a clean cache
             tl = train_bench(a2, 0, 1, device, False)

@@ -153,12 +153,16 @@ def _torchrun_bench(extra, timeout=600):
     return json.loads(lines[0])
 
 
-def test_bench_under_torchrun_takes_the_rccl_path_with_one_rank():
+def test_bench_under_torchrun_takes_the_rccl_path_with_one_rank(tmp_path):
     """the multi-GPU entry of bench.py run the way the driver runs it, on the one GPU a test box has."""
     res = _torchrun_bench(["--tiny", "--height", "128", "--width", "256", "--num-inference-steps", "2", "--steps", "1",
-                           "--warmup", "1", "--batch", "2", "--no-cpu-baseline", "--no-kernel-events"])
+                           "--warmup", "1", "--batch", "2", "--no-cpu-baseline", "--no-kernel-events",
+                           "--dump-outputs", str(tmp_path)])
     assert res["n_gpus"] == 1 and res["value"] > 0 and "rccl process group, 1 rank" in res["config"]["collectives"]
     assert res["scaling"] == "weak" and res["config"]["candidates_per_gpu"] == 2
+    assert res["ms_per_step"] > 0
+    lat = np.load(tmp_path / "latents.npy")      # the gathered latents of the last timed rollout
+    assert lat.dtype == np.float32 and lat.shape == (2, 14, 4, 16, 32) and np.isfinite(lat).all()
     # strong-scaling form: a fixed request of 3 candidates sharded over the (one) rank
     res = _torchrun_bench(["--tiny", "--height", "128", "--width", "256", "--num-inference-steps", "2", "--steps", "1",
                            "--warmup", "0", "--total-candidates", "3", "--no-cpu-baseline", "--no-kernel-events"])

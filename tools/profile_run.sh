@@ -14,9 +14,9 @@ python tools/pmc_summary.py $O/${TAG}_pmc_1step.csv $(find /tmp/pmc1 /tmp/pmc2 /
 # the temporal block alone (MFMA pipe of temporal_block_resident_kernel (C = 320) / temporal_block_kernel at the level shapes; PMC in its own pass)
 timeout 200 rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE -d /tmp/pmc_t -o pt -- env ONLY_FUSED=1 ITERS=5 python tools/temporal_probe.py > $O/pmc_temporal.log 2>&1
 python tools/pmc_summary.py $O/${TAG}_pmc_temporal_probe.csv $(find /tmp/pmc_t -name "*results.db")
-# the default line (what the driver runs: `box` calibration, `extra` legs = B = 8, fp16, fp16 + fp32 stream, 2 training steps)
-timeout 600 python bench.py --dump-shapes $O/${TAG}_shapes.txt 2>/dev/null | tail -1 > $O/${TAG}_bench.json; cut -c1-300 $O/${TAG}_bench.json
+# the --full line (`box` calibration, per-launch events, `extra` legs = B = 8, fp16, fp16 + fp32 stream, 2 training steps)
+timeout 600 python bench.py --full --dump-shapes $O/${TAG}_shapes.txt 2>/dev/null | tail -1 > $O/${TAG}_bench.json; cut -c1-300 $O/${TAG}_bench.json
 timeout 300 python bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-extras --end-to-end 2>/dev/null | tail -1 > $O/${TAG}_bench_e2e.json
 grep temporal $O/${TAG}_pmc_1step.csv $O/${TAG}_pmc_temporal_probe.csv
 # the <= 1e-3 configuration with per-family rows (fp16 + fp32 residual stream)
-timeout 300 python bench.py --dtype fp16 --residual-fp32 --steps 1 --warmup 1 --no-cpu-baseline 2>/dev/null | tail -1 > $O/${TAG}_bench_fp16_res32.json; cut -c1-200 $O/${TAG}_bench_fp16_res32.json
+timeout 300 python bench.py --full --dtype fp16 --residual-fp32 --steps 1 --warmup 1 --no-cpu-baseline 2>/dev/null | tail -1 > $O/${TAG}_bench_fp16_res32.json; cut -c1-200 $O/${TAG}_bench_fp16_res32.json

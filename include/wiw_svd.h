@@ -200,6 +200,14 @@ int wiw_attn_spatial_bf16(void* stream, const void* QK, int ldqk, int k_col_off,
 int wiw_attn_spatial_ps_bf16(void* stream, const void* QK, int ldqk, int k_col_off, const void* Vt, int64_t ldvt,
                              void* O, int ldo, int frames, int S, int heads, const void* zeros);
 
+/* The same operator for ANY token count S >= 1 (the latent sizes whose inner levels have S % 8 != 0, e.g. 7x7 and 14x14 at a
+ * 448x448 output): pre-scaled Q as above, the kernel of wiw_attn_spatial_bf16 on a FRAME-PADDED V^T,
+ *   Vt[h*64 + d][n*Sv + s], Sv % 8 == 0, Sv >= S, columns S .. Sv-1 of every frame zero (wiw_transpose_framepad_bf16),
+ * so that each frame's keys start on a 16-byte boundary.  QK and O rows stay dense ([frames*S][ld]); ldvt >= frames * Sv,
+ * ldo % 8 == 0. */
+int wiw_attn_spatial_ps_padded_bf16(void* stream, const void* QK, int ldqk, int k_col_off, const void* Vt, int64_t ldvt,
+                                    void* O, int ldo, int frames, int S, int Sv, int heads, const void* zeros);
+
 /* ------------------------------------------------------------------------------------------------
  * Temporal self-attention over the T (<= 16) frames of every spatial site, head_dim 64:
  * rows of site (b, s) are m = (b*T + t)*S + s — the (B*S, T, C) permutes of
@@ -459,6 +467,10 @@ int wiw_attn_small_bf16(void* stream, const void* QK, int ldqk, int k_col_off, c
  * wiw_attn_spatial_bf16 its V^T operand from the V columns of ONE fused q|k|v projection (to_q / to_k / to_v of
  * dp/models/attention_processor.py:2358-2366 as a single GEMM).  rows, C, c0, ldx, ldy multiples of 8. */
 int wiw_transpose_bf16(void* stream, const void* X, int64_t ldx, int c0, int64_t rows, int C, void* Y, int64_t ldy);
+/* Y[c][n*Sv + s] = X[n*S + s][c0 + c] for s < S and 0 for S <= s < Sv, frames n < `frames`: the frame-padded V^T of
+ * wiw_attn_spatial_ps_padded_bf16 for any S >= 1.  Sv, C, c0, ldx, ldy multiples of 8; ldy >= frames * Sv. */
+int wiw_transpose_framepad_bf16(void* stream, const void* X, int64_t ldx, int c0, int frames, int S, int Sv, int C, void* Y,
+                                int64_t ldy);
 
 /* ------------------------------------------------------------------------------------------------
  * Fine-tuning step (FTsvd/train_svd.py:844-970) — first entries of that row; the operators' backward kernels are not built.

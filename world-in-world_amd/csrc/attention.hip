@@ -12,6 +12,8 @@
 // that own the query column — the O^T accumulator has the same column ownership, so rescaling needs no cross-lane traffic.
 #include <stdlib.h>
 
+#include <type_traits>
+
 #include "common.h"
 
 namespace {
@@ -55,12 +57,26 @@ constexpr int KV_STAGE = 16384;   // K tile + V^T tile
 // WLSE (the fine-tuning forward): also writes the row log-sum-exp in the log2 domain, lse[(frame * heads + h) * S + q] =
 // log2 sum_k 2^(s_qk c), from fp32 sums of the UN-rounded probabilities — what wiw_attn_bwd_bf16 otherwise recomputes with a
 // whole Q.K^T pass (train.hip, pass 1 of the dQ kernel).  32 more VALU adds per tile; the inference instantiation has none.
-template <int NWV, bool WLSE>
+// PADV (wiw_attn_spatial_ps_padded_bf16): the V^T columns of frame n start at n * Sv (Sv % 8 == 0, Sv >= S, columns S .. Sv-1
+// zero: wiw_transpose_framepad_bf16) instead of n * S, so every frame's keys start on a 16-byte boundary for any S; K, Q and O
+// rows stay dense at n * S.  The straddling last V^T chunk of a frame reads those zeros (masked P = 0 times a NaN would not be
+// 0).  The last kernel argument is Sv (PADV) or the lse pointer (the others): the instantiations of the dense V^T keep the
+// kernel-argument layout, and so the code, they had before PADV existed.
+template <bool PADV>
+using attn_tail_t = typename std::conditional<PADV, int64_t, float* __restrict__>::type;
+WIW_DEV float* tail_lse(float* p) { return p; }
+WIW_DEV float* tail_lse(int64_t) { return nullptr; }
+WIW_DEV int64_t tail_sv(float*) { return 0; }
+WIW_DEV int64_t tail_sv(int64_t sv) { return sv; }
+
+template <int NWV, bool WLSE, bool PADV>
 __global__ __launch_bounds__(NWV * 64, WIW_ATTN_MIN_WAVES) void attn_spatial_kernel(const uint16_t* __restrict__ QK, int ldqk, int k_col_off,
                                                                const uint16_t* __restrict__ Vt, int64_t ldvt,
                                                                uint16_t* __restrict__ O, int ldo, int S, int heads,
                                                                int q_tiles, float scale_log2e, const char* zeros,
-                                                               float* __restrict__ lse) {
+                                                               attn_tail_t<PADV> tail) {
+    float* __restrict__ lse = tail_lse(tail);
+    const int64_t Sv = tail_sv(tail);
     constexpr int QB = NWV * 32;
     constexpr int NI = 8 / NWV;        // 8-row DMA instructions per wave and operand tile (64 rows): 2 or 1
     __shared__ __attribute__((aligned(16))) char smem[2 * KV_STAGE];
@@ -76,6 +92,7 @@ __global__ __launch_bounds__(NWV * 64, WIW_ATTN_MIN_WAVES) void attn_spatial_ker
     const int fh = bid / q_tiles;
     const int h = fh % heads, n = fh / heads;
     const int64_t row0 = (int64_t)n * S;
+    const int64_t vcol0 = PADV ? n * Sv : row0;   // first V^T column of this frame
     const int fr = lane & 15, fq = lane >> 4;
 
     // ---- Q^T B-operands straight from global: lane (query fr, d chunk fq) -> 8 consecutive d
@@ -100,7 +117,7 @@ __global__ __launch_bounds__(NWV * 64, WIW_ATTN_MIN_WAVES) void attn_spatial_ker
     // for the three DMA loads just issued, i.e. a full memory round trip per tile and wave.
     const int r0 = wave * NI * 8 + rsub;                    // row of the tile for instruction 0 (key for K, d for V^T)
     const char* kp0 = (const char*)(QK + (row0 + r0) * ldqk + k_col_off + h * 64 + (pos ^ (r0 & 7)) * 8);
-    const char* vp0 = (const char*)(Vt + (int64_t)(h * 64 + r0) * ldvt + row0 + (pos ^ ((r0 >> 1) & 7)) * 8);
+    const char* vp0 = (const char*)(Vt + (int64_t)(h * 64 + r0) * ldvt + vcol0 + (pos ^ ((r0 >> 1) & 7)) * 8);
     const int64_t kstep = (int64_t)KB * ldqk * 2;
     const int64_t k8 = (int64_t)8 * ldqk * 2;               // 8 K rows
     // V^T rows 8 further on: the chunk position pos ^ sw becomes pos ^ sw ^ 4
@@ -121,7 +138,8 @@ __global__ __launch_bounds__(NWV * 64, WIW_ATTN_MIN_WAVES) void attn_spatial_ker
 #pragma unroll
             for (int i = 0; i < NI; ++i) {
                 const int r = (wave * NI + i) * 8 + rsub;
-                // K rows past the end re-read the last key (masked to -inf below); V^T chunks past the end read zeros
+                // K rows past the end re-read the last key (masked to -inf below); V^T chunks past the end read zeros (PADV: a
+                // chunk that straddles the end reads the frame's zero padding)
                 const int key = kt * KB + r;
                 const char* ksrc = key < S ? kp_(i) : kp_(i) - (int64_t)(key - (S - 1)) * ldqk * 2;
                 glds16(ksrc, sK + i * 1024);
@@ -390,27 +408,29 @@ __global__ __launch_bounds__(256) void attn_temporal_kernel(const uint16_t* __re
 
 }  // namespace
 
+// Sv == 0: the dense V^T of wiw_attn_spatial_bf16 (frame n at column n * S, S % 8 == 0); Sv > 0: the frame-padded one
 static int attn_spatial_launch(void* stream, const void* QK, int ldqk, int k_col_off, const void* Vt, int64_t ldvt, void* O, int ldo,
-                               int frames, int S, int heads, float scale_log2e, const void* zeros, float* lse) {
+                               int frames, int S, int heads, float scale_log2e, const void* zeros, float* lse, int Sv = 0) {
     WIW_REQUIRE(QK && Vt && O && zeros, "attn_spatial: null pointer");
     WIW_REQUIRE(frames > 0 && S > 0 && heads > 0, "attn_spatial: bad sizes");
-    WIW_REQUIRE(S % 8 == 0, "attn_spatial: S (= h*w of the level) must be a multiple of 8");
+    WIW_REQUIRE(Sv > 0 || S % 8 == 0, "attn_spatial: S (= h*w of the level) must be a multiple of 8");
     WIW_REQUIRE(ldqk % 8 == 0 && k_col_off % 8 == 0 && ldvt % 8 == 0 && ldo % 4 == 0, "attn_spatial: misaligned strides");
     // 8 waves (256 queries) per staged KV tile halve the LDS-DMA instructions per flop but measured 9-10 % SLOWER at
     // S = 9216 / 2304 (3.80 vs 3.45 ms, profiles/r06q_attn_probe.txt: twice the waves behind every tile barrier); A/B knob
     static const bool want8 = getenv("WIW_ATTN_8WAVES") != nullptr;
-    const bool big = S >= 2048 && want8 && lse == nullptr;
+    const bool big = S >= 2048 && want8 && lse == nullptr && Sv == 0;
     const int qb = big ? 256 : 128;
     const int q_tiles = (S + qb - 1) / qb;
     const int64_t nb = (int64_t)q_tiles * heads * frames;
     WIW_REQUIRE(nb < (1ll << 31), "attn_spatial: grid too large");
-#define WIW_ATTN_LAUNCH(NW, WL)                                                                                                    \
-    hipLaunchKernelGGL((attn_spatial_kernel<NW, WL>), dim3((unsigned)nb), dim3(NW * 64), 0, (hipStream_t)stream, (const uint16_t*)QK, \
-                       ldqk, k_col_off, (const uint16_t*)Vt, ldvt, (uint16_t*)O, ldo, S, heads, q_tiles, scale_log2e,              \
-                       (const char*)zeros, lse)
-    if (lse) WIW_ATTN_LAUNCH(4, true);
-    else if (big) WIW_ATTN_LAUNCH(8, false);
-    else WIW_ATTN_LAUNCH(4, false);
+#define WIW_ATTN_LAUNCH(NW, WL, PV, TAIL)                                                                                              \
+    hipLaunchKernelGGL((attn_spatial_kernel<NW, WL, PV>), dim3((unsigned)nb), dim3(NW * 64), 0, (hipStream_t)stream,                 \
+                       (const uint16_t*)QK, ldqk, k_col_off, (const uint16_t*)Vt, ldvt, (uint16_t*)O, ldo, S, heads, q_tiles,     \
+                       scale_log2e, (const char*)zeros, TAIL)
+    if (Sv > 0) WIW_ATTN_LAUNCH(4, false, true, (int64_t)Sv);
+    else if (lse) WIW_ATTN_LAUNCH(4, true, false, lse);
+    else if (big) WIW_ATTN_LAUNCH(8, false, false, lse);
+    else WIW_ATTN_LAUNCH(4, false, false, lse);
 #undef WIW_ATTN_LAUNCH
     return wiw_check_launch("wiw_attn_spatial_bf16");
 }
@@ -426,6 +446,18 @@ extern "C" int wiw_attn_spatial_bf16(void* stream, const void* QK, int ldqk, int
 int wiw_attn_spatial_prescaled_fallback(void* stream, const void* QK, int ldqk, int k_col_off, const void* Vt, int64_t ldvt, void* O,
                                         int ldo, int frames, int S, int heads, const void* zeros) {
     return attn_spatial_launch(stream, QK, ldqk, k_col_off, Vt, ldvt, O, ldo, frames, S, heads, 1.0f, zeros, nullptr);
+}
+
+// The first form on a pre-scaled Q and a frame-padded V^T (any S >= 1): the levels whose token count is not a multiple of 8
+extern "C" int wiw_attn_spatial_ps_padded_bf16(void* stream, const void* QK, int ldqk, int k_col_off, const void* Vt, int64_t ldvt,
+                                               void* O, int ldo, int frames, int S, int Sv, int heads, const void* zeros) {
+    WIW_REQUIRE(QK && Vt && O && zeros, "attn_spatial_ps_padded: null pointer");
+    WIW_REQUIRE(frames > 0 && S > 0 && heads > 0, "attn_spatial_ps_padded: bad sizes");
+    WIW_REQUIRE(Sv >= S && Sv % 8 == 0, "attn_spatial_ps_padded: the V^T frame stride Sv must be a multiple of 8 and >= S");
+    WIW_REQUIRE(ldqk % 8 == 0 && k_col_off % 8 == 0 && ldvt % 8 == 0 && ldo % 8 == 0, "attn_spatial_ps_padded: misaligned strides");
+    WIW_REQUIRE(ldqk >= k_col_off + heads * 64 && ldo >= heads * 64 && ldvt >= (int64_t)frames * Sv,
+                "attn_spatial_ps_padded: strides smaller than the operands");
+    return attn_spatial_launch(stream, QK, ldqk, k_col_off, Vt, ldvt, O, ldo, frames, S, heads, 1.0f, zeros, nullptr, Sv);
 }
 
 extern "C" int wiw_attn_spatial_lse_bf16(void* stream, const void* QK, int ldqk, int k_col_off, const void* Vt,

@@ -180,6 +180,59 @@ extern "C" int wiw_transpose_bf16(void* stream, const void* X, int64_t ldx, int 
 }
 
 namespace {
+// Y[c][n*Sv + s] = X[n*S + s][c0 + c] for s < S, 0 for S <= s < Sv: the V^T operand of wiw_attn_spatial_ps_padded_bf16 (any
+// S; Sv % 8 == 0).  64 output columns x 64 channels per block; a source row is gathered per output column, so frame ends need
+// no alignment on the X side.  Only the levels whose token count is not a multiple of 8 take it (small S).
+__global__ __launch_bounds__(256) void transpose_framepad_kernel(const uint16_t* __restrict__ X, int64_t ldx, int c0, int S, int Sv,
+                                                                 int64_t ncol, int C, uint16_t* __restrict__ Y, int64_t ldy) {
+    __shared__ __attribute__((aligned(16))) uint16_t tile[64][72];   // [channel][output column]
+    const int64_t j0 = (int64_t)blockIdx.x * 64;
+    const int cb = blockIdx.y * 64;
+    const int tid = threadIdx.x;
+#pragma unroll
+    for (int it = 0; it < 2; ++it) {
+        const int i = tid + it * 256;
+        const int jj = i >> 3, ch = i & 7;                        // output column j0 + jj, 16-byte chunk of 8 channels
+        const int64_t j = j0 + jj;
+        uint4 a = uint4{0u, 0u, 0u, 0u};
+        if (j < ncol && cb + ch * 8 < C) {
+            const int64_t n = j / Sv;
+            const int s = (int)(j - n * Sv);
+            if (s < S) a = *(const uint4*)(X + (n * S + s) * ldx + c0 + cb + ch * 8);
+        }
+        const uint32_t au[4] = {a.x, a.y, a.z, a.w};
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            tile[ch * 8 + 2 * e][jj] = (uint16_t)(au[e] & 0xffffu);
+            tile[ch * 8 + 2 * e + 1][jj] = (uint16_t)(au[e] >> 16);
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int it = 0; it < 2; ++it) {
+        const int i = tid + it * 256;
+        const int c = i >> 3, ch = i & 7;                         // output row c, 8 consecutive output columns
+        if (cb + c < C && j0 + ch * 8 < ncol)                     // ncol % 8 == 0: a chunk is inside or outside as a whole
+            *(uint4*)(Y + (int64_t)(cb + c) * ldy + j0 + ch * 8) = *(const uint4*)&tile[c][ch * 8];
+    }
+}
+}  // namespace
+
+extern "C" int wiw_transpose_framepad_bf16(void* stream, const void* X, int64_t ldx, int c0, int frames, int S, int Sv, int C, void* Y,
+                                           int64_t ldy) {
+    WIW_REQUIRE(X && Y, "transpose_framepad: null pointer");
+    WIW_REQUIRE(frames > 0 && S > 0 && C > 0, "transpose_framepad: bad sizes");
+    WIW_REQUIRE(Sv >= S && Sv % 8 == 0, "transpose_framepad: the frame stride Sv must be a multiple of 8 and >= S");
+    WIW_REQUIRE(C % 8 == 0 && c0 % 8 == 0 && ldx % 8 == 0 && ldy % 8 == 0, "transpose_framepad: C, c0, ldx, ldy must be multiples of 8");
+    const int64_t ncol = (int64_t)frames * Sv;
+    WIW_REQUIRE(ldx >= c0 + C && ldy >= ncol, "transpose_framepad: strides smaller than the operands");
+    WIW_REQUIRE((ncol + 63) / 64 < (1ll << 31), "transpose_framepad: grid too large");
+    hipLaunchKernelGGL(transpose_framepad_kernel, dim3((unsigned)((ncol + 63) / 64), (unsigned)((C + 63) / 64)), dim3(256), 0,
+                       (hipStream_t)stream, (const uint16_t*)X, ldx, c0, S, Sv, ncol, C, (uint16_t*)Y, ldy);
+    return wiw_check_launch("wiw_transpose_framepad_bf16");
+}
+
+namespace {
 // out[i] = round16(X[i]): the 16-bit MFMA operand of an fp32 residual-stream tensor (ABI 11); 8 values per thread
 __global__ __launch_bounds__(256) void cast_f32_to_16_kernel(const float* __restrict__ X, int64_t n8, uint16_t* __restrict__ out) {
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n8; i += (int64_t)gridDim.x * 256) {

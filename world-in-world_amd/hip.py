@@ -107,6 +107,8 @@ EXPORTS = {
                                         C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p]),
     "wiw_attn_spatial_ps_bf16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p,
                                            C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "wiw_attn_spatial_ps_padded_bf16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p,
+                                                  C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "wiw_attn_spatial_lse_bf16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p,
                                             C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p]),
     "wiw_attn_bwd_given_lse_bf16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
@@ -166,6 +168,8 @@ EXPORTS = {
     "wiw_cfg_euler_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float,
                                      C.c_float, C.c_float, C.c_float]),
     "wiw_transpose_bf16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_int64]),
+    "wiw_transpose_framepad_bf16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                              C.c_void_p, C.c_int64]),
     "wiw_ema_step_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_float]),
     "wiw_adamw_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_float,
                                  C.c_float, C.c_float, C.c_float, C.c_float, C.c_int]),
@@ -251,6 +255,7 @@ class Hip:
         # entries are (start_event, end_event, algorithmic_flops, mode, (M, N, K, epilogue))
         self.gemm_profile = None
         self._splitk_ws = None
+        self._splitk_ws_outgrown = []     # earlier, smaller split-K workspaces (captured graphs may still address them)
         self.gn_two_kernels = bool(os.environ.get("WIW_GN_TWO_KERNELS"))     # A/B knob: statistics + apply launches at every level
         # int32 counters of the GroupNorm statistics launches, one row per STREAM that ever launched one (see _gn_buffers);
         # all rows are allocated and zeroed here: handing one out is legal inside a hipGraph capture
@@ -333,6 +338,10 @@ class Hip:
         if splitk > 1:   # fp32 partial sums of the K ranges: one grow-only scratch buffer per Hip (stream-ordered reuse)
             need = splitk * M * N
             if self._splitk_ws is None or self._splitk_ws.numel() < need:
+                # the outgrown buffer is KEPT: a forward captured earlier (pipeline.GraphedForward) replays with its address —
+                # freeing it when a larger batch grows the workspace left that graph writing into released memory
+                if self._splitk_ws is not None:
+                    self._splitk_ws_outgrown.append(self._splitk_ws)
                 self._splitk_ws = torch.empty(need, dtype=torch.float32, device=self.device)
             a.splitk, a.workspace = splitk, self._splitk_ws.data_ptr()
         if self.gemm_profile is None:
@@ -367,6 +376,13 @@ class Hip:
         self._timed("attn_spatial", 4.0 * frames * heads * S * S * 64, 8.0 * frames * S * heads * 64, lambda: self._ck(
             self.lib.wiw_attn_spatial_ps_bf16(self._stream(), _p(QK), ldqk, k_col_off, _p(Vt), ldvt, _p(O), ldo,
                                               frames, S, heads, self.zeros.data_ptr()), "wiw_attn_spatial_ps_bf16"))
+        return O
+
+    def attn_spatial_ps_padded(self, QK, ldqk, k_col_off, Vt, ldvt, O, ldo, frames, S, Sv, heads):
+        """`attn_spatial_ps` for any S >= 1: V^T frame n starts at column n * Sv (`transpose_framepad`, Sv % 8 == 0)."""
+        self._timed("attn_spatial", 4.0 * frames * heads * S * S * 64, 8.0 * frames * S * heads * 64, lambda: self._ck(
+            self.lib.wiw_attn_spatial_ps_padded_bf16(self._stream(), _p(QK), ldqk, k_col_off, _p(Vt), ldvt, _p(O), ldo,
+                                                     frames, S, Sv, heads, self.zeros.data_ptr()), "wiw_attn_spatial_ps_padded_bf16"))
         return O
 
     def attn_temporal(self, QKV, ldqkv, O, ldo, batch, T, S, heads, scale):
@@ -651,6 +667,13 @@ class Hip:
         """Y[c][r] = X[r][c0 + c] (bf16)."""
         self._timed("transpose", 0.0, 4.0 * rows * Cn, lambda: self._ck(
             self.lib.wiw_transpose_bf16(self._stream(), _p(X), ldx, c0, rows, Cn, _p(Y), ldy), "wiw_transpose_bf16"))
+        return Y
+
+    def transpose_framepad(self, X, ldx, c0, frames, S, Sv, Cn, Y, ldy):
+        """Y[c][n*Sv + s] = X[n*S + s][c0 + c], zero for S <= s < Sv (16-bit): the V^T of `attn_spatial_ps_padded`."""
+        self._timed("transpose", 0.0, 2.0 * frames * (S + Sv) * Cn, lambda: self._ck(
+            self.lib.wiw_transpose_framepad_bf16(self._stream(), _p(X), ldx, c0, frames, S, Sv, Cn, _p(Y), ldy),
+            "wiw_transpose_framepad_bf16"))
         return Y
 
     def adamw_step(self, p, g, m, v, step, lr, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=1e-2, p16=None):

@@ -371,7 +371,14 @@ def validate_args(args) -> None:
     None`); the general Sk > 1 cross-attention exists below the server (UNetHIP(num_past_obs=P), csrc/cross_attn.hip) for the
     offline / training callers that build (B, P, 1024) embeddings themselves (train_svd.py:889-894); an action
     embedder width the task cannot produce (navigation: one channel per frame, get_action_ids micro_cond; manipulation: 10 =
-    [norm_xyz | r6 | norm_grip] or num_frames + 9, its positional form — utils/svd_utils.py:418-457, 499-567)."""
+    [norm_xyz | r6 | norm_grip] or num_frames + 9, its positional form — utils/svd_utils.py:418-457, 499-567); an output
+    --width / --height that is not a multiple of 64 (the 1/8 latent goes through three 2x downsamples of the UNet).  Any
+    multiple of 64 is served: the spatial attention takes every token count (e.g. 7x7 and 14x14 at 448x448)."""
+    for flag in ("width", "height"):
+        v = getattr(args, flag, None)
+        if v is not None and (v <= 0 or v % 64 != 0):
+            raise SystemExit(f"--{flag} {v}: the output size must be a positive multiple of 64 (the latent is 1/8 of it and "
+                             f"the UNet halves it three times)")
     if args.num_past_obs != 1:
         raise SystemExit(f"--num_past_obs {args.num_past_obs}: the WM-server protocol carries ONE conditioning image per candidate "
                          f"(the reference's served path asserts past_obs_pixel is None, eval_inference.py:236-242); P > 1 tokens are "

@@ -695,7 +695,8 @@ class UNetHIP:
             assert not (fold_qkv or legacy), "A/B knobs of the 16-bit stream"
         if not fold_qkv:
             a = hip.layernorm(h, M, Cn, w[b + ".norm1.weight"], w[b + ".norm1.bias"], out=xn)
-        vt = self._empty(Cn, M)
+        Sv = -(-S // 8) * 8      # V^T frame stride: S, or the next multiple of 8 (frame-padded V^T, any latent size)
+        vt = self._empty(Cn, frames * Sv)
         o = self._empty(M, Cn)
         # ONE q|k|v projection (the activation is read once), then a 64x64-tiled transpose of the V columns
         qkv = self._empty(M, 3 * Cn)
@@ -704,8 +705,12 @@ class UNetHIP:
                      lnfold=w[b + ".attn1.to_qkv.lnfold.st"], ln_eps=1e-5)
         else:
             hip.gemm(a, w[b + ".attn1.to_qkv.weight"], qkv, M=M, N=3 * Cn, K=Cn, C1=Cn)
-        hip.transpose(qkv, 3 * Cn, 2 * Cn, M, Cn, vt, M)
-        hip.attn_spatial_ps(qkv, 3 * Cn, Cn, vt, M, o, Cn, frames, S, heads)    # Q arrives pre-scaled (to_qkv weights)
+        if Sv == S:
+            hip.transpose(qkv, 3 * Cn, 2 * Cn, M, Cn, vt, M)
+            hip.attn_spatial_ps(qkv, 3 * Cn, Cn, vt, M, o, Cn, frames, S, heads)    # Q arrives pre-scaled (to_qkv weights)
+        else:   # S % 8 != 0 (e.g. the 14x14 and 7x7 levels of a 448x448 output): each frame's keys start at column n * Sv
+            hip.transpose_framepad(qkv, 3 * Cn, 2 * Cn, frames, S, Sv, Cn, vt, frames * Sv)
+            hip.attn_spatial_ps_padded(qkv, 3 * Cn, Cn, vt, frames * Sv, o, Cn, frames, S, Sv, heads)
         # The adds that follow a GEMM in the reference — the single-key cross-attention output (one vector per CFG item,
         # attention.py:545-551, 740-743) and the frame-position embedding (transformer_temporal.py:352-353) — ride in that
         # GEMM's epilogue as its per-row-group vector, so every LayerNorm below is a plain one-read / one-write pass.

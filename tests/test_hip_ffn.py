@@ -314,7 +314,7 @@ def test_ffn_out16_without_fp32_x(hip):
 
 # ----------------------------------------------------------------------------------------------------------------------
 # wiw_ffn32_geglu (csrc/ffn32.hip, ABI 14): the same operator on 32x32x16 MFMAs, everything in registers.  Same oracle, same
-# gates.  (Opt-in in the UNet — WIW_FFN32=1 — because it is not faster than ffn.hip; it is kept correct.)
+# gates.  (Not used by the UNet because it is not faster than ffn.hip; it is kept correct.)
 # ----------------------------------------------------------------------------------------------------------------------
 def make_weights32(dtype, seed=0, gamma=None, beta=None):
     from wiw_amd.unet import pack_ffn32

@@ -366,11 +366,7 @@ def test_groupnorm_onepass(hip, n, c1, c2, h, w):
         check(from_nhwc(out, n, h, w), ref, what=f"one-pass groupnorm C={c1}+{c2} {h}x{w} silu={silu}")
         again = hip.groupnorm(x1, c1, x2, c2, rows, h * w, dev_f(gamma), dev_f(beta), 1e-5, silu)
         assert torch.equal(out, again)
-        hip.gn_two_kernels = True
-        try:
-            two = hip.groupnorm(x1, c1, x2, c2, rows, h * w, dev_f(gamma), dev_f(beta), 1e-5, silu)
-        finally:
-            hip.gn_two_kernels = False
+        two = hip.groupnorm(x1, c1, x2, c2, rows, h * w, dev_f(gamma), dev_f(beta), 1e-5, silu, two_kernels=True)
         d = (out.float() - two.float()).abs().max().item()
         print(f"[gn one pass] C={c1}+{c2} {h}x{w} silu={silu}: max |one pass - two launches| = {d:.3e}")
         assert d <= 0.05          # one 16-bit ulp at the largest magnitudes: the statistics differ in the last fp32 bits only

@@ -27,7 +27,6 @@ K_CMAJOR = 512   # conv modes: K of W is channel-block major, k = ((c / 64) * ta
 GEGLU_TILE = 80  # value|gate half-tile width of the packed GEGLU weights (gemm.hip BN / 2)
 FFN_CHUNK = 64   # hidden units per chunk of the fused FeedForward kernel (ffn.hip): W1 rows in chunks of [64 value | 64 gate]
 FFN_C, FFN_HIDDEN = 320, 1280   # the one shape wiw_ffn_geglu_bf16 is built for
-_GN_RPB_R5 = bool(os.environ.get("WIW_GN_RPB_R5"))
 PROF_RES1, PROF_RES2 = 1 << 24, 1 << 25   # bench.py profile keys only: the launch read a res1 / res2 operand
 
 
@@ -256,7 +255,6 @@ class Hip:
         self.gemm_profile = None
         self._splitk_ws = None
         self._splitk_ws_outgrown = []     # earlier, smaller split-K workspaces (captured graphs may still address them)
-        self.gn_two_kernels = bool(os.environ.get("WIW_GN_TWO_KERNELS"))     # A/B knob: statistics + apply launches at every level
         # int32 counters of the GroupNorm statistics launches, one row per STREAM that ever launched one (see _gn_buffers);
         # all rows are allocated and zeroed here: handing one out is legal inside a hipGraph capture
         # 40 rows: torch hands out at most 32 pooled streams + the default stream + the graph-capture stream (10 MB)
@@ -485,13 +483,6 @@ class Hip:
         # blocks win at the two outer levels — per-frame 72x128: 128 -> 256 rows 38.7 -> 32.7 us (C = 320), 65.6 -> 59.1 (C = 640);
         # per-frame 36x64: 64 -> 128 rows 23.3 -> 21.0 us (C = 640), 34.7 -> 32.5 (C = 1280; 256 is slower there); per-clip 36x64
         # (32 256 rows): 64 -> 128 rows 28.0 -> 25.9 us.  The inner levels run the one-pass kernel and do not come here.
-        if _GN_RPB_R5:      # A/B knob WIW_GN_RPB_R5=1: the block sizes of rounds 4-5
-            if not clip:
-                return 128 if rows_per_unit >= 8192 else (64 if rows_per_unit >= 2048 else (32 if rows_per_unit >= 512 else 16))
-            rpb = 16
-            while rpb < 256 and rpb * 2 * 448 <= rows_per_unit:
-                rpb *= 2
-            return rpb
         if not clip:
             return 256 if rows_per_unit >= 8192 else (128 if rows_per_unit >= 2048 else (32 if rows_per_unit >= 512 else 16))
         rpb = 16
@@ -528,18 +519,18 @@ class Hip:
         torch.cuda.synchronize(self.device)
         return int(self._gn_cnt_pool.abs().max()) == 0
 
-    def groupnorm(self, X1, C1, X2, C2, rows, rows_per_unit, gamma, beta, eps, silu, out=None, clip=False, raw16=None):
+    def groupnorm(self, X1, C1, X2, C2, rows, rows_per_unit, gamma, beta, eps, silu, out=None, clip=False, raw16=None,
+                  two_kernels=False):
         """statistics (deterministic, no atomics) -> fused finalize + apply; returns the normalised (and SiLU'd) bf16
         tensor [rows, C1+C2].  clip=True: the unit is a whole clip (T frames), see gn_rows_per_block.
         fp32 residual stream (ABI 11): fp32 X1 (and X2) select the fp32-input kernels; `raw16` (16-bit [rows, C1 + C2]) then
-        also receives the rounded raw input (the operand of the 1x1 conv_shortcut)."""
+        also receives the rounded raw input (the operand of the 1x1 conv_shortcut).
+        two_kernels=True: the statistics + apply launches even where the one-pass kernel would run (tests compare the two)."""
         f32in = X1.dtype == torch.float32
         assert X2 is None or (X2.dtype == torch.float32) == f32in, "groupnorm: X1 and X2 must have one dtype"
         assert raw16 is None or f32in, "groupnorm: raw16 only with fp32 inputs"
-        if os.environ.get("WIW_GN_UNFUSED") and not f32in:   # A/B knob for profiling
-            return self.groupnorm_unfused(X1, C1, X2, C2, rows, rows_per_unit, gamma, beta, eps, silu, out, clip)
         Ct = C1 + C2
-        if (not f32in and not clip and not self.gn_two_kernels
+        if (not f32in and not clip and not two_kernels
                 and self.lib.wiw_groupnorm_onepass_ok(C1, C2, rows, rows_per_unit)):      # ABI 15: the two inner levels in ONE pass
             if out is None:
                 out = torch.empty((rows, Ct), dtype=self.dtype, device=self.device)

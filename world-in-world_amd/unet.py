@@ -162,7 +162,7 @@ def _require_single_key(ehs: torch.Tensor, max_tokens: int = 1) -> None:
 
 class UNetHIP:
     def __init__(self, cfg: UNetConfig, state_dict: Dict[str, "torch.Tensor | np.ndarray"], device="cuda:0",
-                 hip: Optional[Hip] = None, dtype: torch.dtype = torch.bfloat16, fold_layernorm: Optional[bool] = None,
+                 hip: Optional[Hip] = None, dtype: torch.dtype = torch.bfloat16, fold_layernorm: bool = False,
                  residual_fp32: "Optional[bool | str]" = None, num_past_obs: int = 1):
         """dtype: 16-bit storage type of weights and activations (bf16, or fp16 = the reference's served default,
         eval_inference.py:294); with `hip` given, its dtype is used.
@@ -175,13 +175,17 @@ class UNetHIP:
                   8.6e-4 max (north_star: 1e-3 relative latent error) at 0.96 x the speed of plain fp16 (profiles/r20b_*).
           "full"  (rounds 4-5) also every sub-block output inside the transformer blocks: 5.1e-4 / 8.6e-4 on the same trajectory,
                   9.1e-4 instead of 1.00e-3 on ONE forward at sigma = 15.6 — at 0.90 x the speed of fp16.
-        Default: env WIW_RES32 (A/B knobs: WIW_RES32_PARTS = rb | tr | both, WIW_RES32_TR_MASK).
+        Default: env WIW_RES32 (set: True).  Why the block level and not the transformers' inner stream (profiles/
+        r20b_res32_parts.txt, same trajectory): fp32 inside the transformer blocks alone still leaves 1.02e-3 max.  The error
+        that accumulates is the rounding of the stream that runs through the WHOLE depth of the network; a transformer block's
+        inner stream starts fresh at proj_in and is folded back into the fp32 block stream at proj_out after 7 adds.
         num_past_obs: conditioning tokens per candidate the replica is built for (--num_past_obs, train_svd.py:359).  1 (every
         launcher of the reference): the two cross-attentions of a layer in closed form.  2..8: also the weights of the general
         form (attn2.to_q / to_k, norm2) and `wiw_cross_attn_fewkeys_bf16`; requests may then carry 1..num_past_obs tokens.
         fold_layernorm: fold norm1 / norm3 / norm_in into their consumer GEMMs at the widths the 256x160 tile serves
-        (WIW_EPI_LNFOLD).  OFF by default: measured -0.7 % on the rollout (the in-kernel row statistics cost the K = 320
-        GEMMs more than the four LayerNorm passes per block they replace); env WIW_LN_FOLD=1 turns it on."""
+        (WIW_EPI_LNFOLD); ignored with the fp32 stream (the folds read the raw stream as a 16-bit MFMA operand).  OFF by
+        default: measured -0.7 % on the rollout (the in-kernel row statistics cost the K = 320 GEMMs more than the four
+        LayerNorm passes per block they replace)."""
         self.cfg = cfg
         if not 1 <= int(num_past_obs) <= 8:
             raise ValueError(f"num_past_obs = {num_past_obs}: 1 .. 8 conditioning tokens per candidate")
@@ -192,54 +196,16 @@ class UNetHIP:
         validate_state_dict(cfg, state_dict)
         self.w: Dict[str, torch.Tensor] = {}
         self.alpha: Dict[str, float] = {}
-        self.no_splitk = bool(os.environ.get("WIW_NO_SPLITK"))     # A/B knob
-        self.legacy_cross_guard = bool(os.environ.get("WIW_LN_ADDVEC"))
-        self.ln_fold = bool(os.environ.get("WIW_LN_FOLD")) if fold_layernorm is None else bool(fold_layernorm)
-        self.temporal_unfused = bool(os.environ.get("WIW_TEMPORAL_UNFUSED"))   # A/B knob: LayerNorm + QKV GEMM + attention
-        # fused FeedForward kernel of the 320-channel level (ffn.hip); A/B knobs: WIW_FF_UNFUSED=1 -> two GEMMs again,
-        # WIW_FFN_NO_LN=1 -> fused FeedForward behind a separate LayerNorm pass
-        self.res32 = bool(os.environ.get("WIW_RES32")) if residual_fp32 is None else bool(residual_fp32)
-        # WHICH part of the stream is fp32 (round 6, profiles/r20b_res32_parts.txt: the reference's 25-step trajectory at 576x1024x14,
-        # fp16 weights — relative latent error rms / max and frames/s on one box, plain fp16 = 6.75e-4 / 1.09e-3, 5.857):
-        #   "rb"   the BLOCK-LEVEL stream only — ResBlock outputs, skip tensors, what enters and leaves a transformer block:
-        #          5.47e-4 / 8.58e-4, 5.613 frames/s = 0.958 x fp16                                  <- the mode (default)
-        #   "tr"   only the hidden stream INSIDE a transformer block (proj_in .. proj_out): 1.02e-3 max, 5.424
-        #   "both" rounds 4-5: 5.12e-4 / 8.56e-4, 5.242 = 0.895 x fp16                               (A/B: WIW_RES32_PARTS=both)
-        # The error that accumulates is the rounding of the stream that runs through the WHOLE depth of the network; a transformer
-        # block's inner stream starts fresh at proj_in and is folded back into the fp32 block stream at proj_out after 7 adds.
-        # `self.res32` is the flag of the code that is running: block level, or a transformer's inside.
         assert residual_fp32 in (None, False, True, "full"), residual_fp32
-        parts = os.environ.get("WIW_RES32_PARTS", "both" if residual_fp32 == "full" else "rb") if self.res32 else "none"
-        assert parts in ("both", "tr", "rb", "none"), parts
-        self.res32_tr, self.res32_rb = parts in ("both", "tr"), parts in ("both", "rb")
-        # finer A/B knob: WHICH hidden-stream tensors of a transformer block are fp32 — bit 0 proj_in's output, 1 attn1.to_out
-        # (spatial), 2 the spatial FeedForward's, 3 ff_in's, 4 attn1.to_out (temporal); "tr" / "both" = 31
-        self.tr_mask = int(os.environ.get("WIW_RES32_TR_MASK", "31" if self.res32_tr else "0")) if self.res32 else 0
-        self.res32_tr = self.tr_mask != 0
-        self.sdt = torch.float32 if self.res32_rb else self.dtype      # dtype of block-level residual-stream tensors
-        if self.res32:
-            self.ln_fold = False          # the folds read the raw stream as a 16-bit MFMA operand
-            # round 6: the fused temporal block runs in this mode too — on the 16-bit ROUNDING of the fp32 stream tensor, which
-            # its producer writes beside it (wiw_ffn_geglu_f32stream2's out16 at C = 320, a cast pass elsewhere).  A/B knob:
-            # WIW_TEMPORAL_UNFUSED_RES32=1 = LayerNorm (fp32 in) + QKV GEMM + attention core, as rounds 4-5
-            self.temporal_unfused = self.temporal_unfused or bool(os.environ.get("WIW_TEMPORAL_UNFUSED_RES32"))
-        # convolution weights with K in channel-block-major order (round 4: the taps of a 64-channel block re-read the same
-        # activation window while it is still in L2; A/B knob WIW_K_TAPMAJOR=1 keeps the tap-major order)
-        self.kc = 0 if os.environ.get("WIW_K_TAPMAJOR") else K_CMAJOR
-        self.halo = not os.environ.get("WIW_CONV_NO_HALO")      # A/B knob: 3x3 convolutions without the halo-staged kernel
-        self.halo_sc = not os.environ.get("WIW_CONV_NO_HALO_SC")  # A/B knob: ... except those with the fused shortcut segment
-        # (fp32 stream: the fused kernel's F32E epilogue takes the fp32 residual / output; round 6, ABI 16: its in-kernel
-        # LayerNorm reads the fp32 x itself — A/B knob WIW_FFN_NO_LN_RES32=1 keeps the f32in LayerNorm pass in front)
-        self.ffn_fused = not os.environ.get("WIW_FF_UNFUSED") and not (self.res32 and os.environ.get("WIW_FF_UNFUSED_RES32"))
-        self.ffn_ln = (self.ffn_fused and not os.environ.get("WIW_FFN_NO_LN")
-                       and not (self.res32 and os.environ.get("WIW_FFN_NO_LN_RES32")))
-        # round 5: the 32x32x16-MFMA form of the fused FeedForward (csrc/ffn32.hip) — correct and bit-repeatable, but NOT faster
-        # than ffn.hip at M = 258 048 (805 vs 804 us: both sit on the same serial sum of MFMA + GEGLU + weight DMA + LDS time,
-        # profiles/r13b_*): opt-in A/B knob, ffn.hip stays the served kernel
-        self.ffn32 = self.ffn_fused and bool(os.environ.get("WIW_FFN32"))
+        if residual_fp32 is None:
+            residual_fp32 = bool(os.environ.get("WIW_RES32"))
+        # The precision plan, fixed for the life of the replica: the block-level stream is fp32 (res32_any), and so is the
+        # hidden stream inside the transformer blocks (res32_tr, "full").  Each forward step is told which one it writes.
+        self.res32_any = bool(residual_fp32)
+        self.res32_tr = residual_fp32 == "full"
+        self.sdt = torch.float32 if self.res32_any else self.dtype      # dtype of block-level residual-stream tensors
+        self.ln_fold = bool(fold_layernorm) and not self.res32_any
         self._prepare(state_dict)
-        self.res32_any = self.res32
-        self.res32 = self.res32_rb        # from here on: the flag of the running code (see WIW_RES32_PARTS above)
 
     # ------------------------------------------------------------------------------------------
     # weight re-layout (once, at load)
@@ -283,45 +249,42 @@ class UNetHIP:
         def halo_level(p):
             return (max_w >> level_of(p)) >= 32
 
+        # Convolution weights have K in channel-block-major order (round 4: the taps of a 64-channel block re-read the same
+        # activation window while it is still in L2).
         def conv3(p, cin_pad=0, halo=True):
             x = self._t(sd, p + ".weight").permute(0, 2, 3, 1)  # OIHW -> OHWI
             if cin_pad and x.shape[-1] < cin_pad:
                 x = torch.cat([x, x.new_zeros(*x.shape[:-1], cin_pad - x.shape[-1])], dim=-1)
             x = x.reshape(x.shape[0], -1)
-            w[p + ".weight"] = (conv_k_cmajor(x, 9) if self.kc else x).to(bf).contiguous()
+            w[p + ".weight"] = conv_k_cmajor(x, 9).to(bf).contiguous()
             w[p + ".bias"] = self._t(sd, p + ".bias").contiguous()
-            # a second copy in the K order of the halo-staged kernel (N % 320 == 0: every ResnetBlock2D convolution of the
-            # served widths): `_conv3` picks it when the request's geometry fits (hip.conv_halo_ok), else the copy above
-            if halo and self.halo and halo_level(p) and x.shape[0] % 320 == 0 and x.shape[1] % (9 * 64) == 0:
+            # a second copy in the K order of the halo-staged kernel, which stages a tile's pixel neighbourhood once per 32-channel
+            # block and reads it at nine offsets instead of fetching it per tap (N % 320 == 0: every ResnetBlock2D convolution of
+            # the served widths): `_conv3` picks it when the request's geometry fits (hip.conv_halo_ok), else the copy above
+            if halo and halo_level(p) and x.shape[0] % 320 == 0 and x.shape[1] % (9 * 64) == 0:
                 w[p + ".weight_h"] = conv_k_halo32(x).to(bf).contiguous()
 
         def convt(p):
             x = self._t(sd, p + ".weight")[:, :, :, 0, 0].permute(0, 2, 1)  # (O,I,3) -> (O,3,I)
             x = x.reshape(x.shape[0], -1)
-            w[p + ".weight"] = (conv_k_cmajor(x, 3) if self.kc else x).to(bf).contiguous()
+            w[p + ".weight"] = conv_k_cmajor(x, 3).to(bf).contiguous()
             w[p + ".bias"] = self._t(sd, p + ".bias").contiguous()
 
         def res(p):
             nonlocal off
             s, t = p + ".spatial_res_block", p + ".temporal_res_block"
             norm(s + ".norm1"); conv3(s + ".conv1"); norm(s + ".norm2"); conv3(s + ".conv2")
-            if s + ".conv_shortcut.weight" in sd and os.environ.get("WIW_UNFUSED_SHORTCUT"):   # A/B knob
-                x = self._t(sd, s + ".conv_shortcut.weight")[:, :, 0, 0]
-                w[s + ".conv_shortcut.weight"] = x.to(bf).contiguous()
-                w[s + ".conv_shortcut.bias"] = self._t(sd, s + ".conv_shortcut.bias").contiguous()
-            elif s + ".conv_shortcut.weight" in sd:
+            if s + ".conv_shortcut.weight" in sd:
                 # the 1x1 shortcut over the (skip-concatenated) block input is a tenth K segment of conv2's implicit
                 # GEMM: W = [conv2 (9*Cout) | shortcut (Cin)], bias = b2 + b_sc — the shortcut tensor is never written
                 x = self._t(sd, s + ".conv_shortcut.weight")[:, :, 0, 0]
                 w2 = self._t(sd, s + ".conv2.weight").permute(0, 2, 3, 1).reshape(x.shape[0], -1)
-                if self.kc:
-                    w2 = conv_k_cmajor(w2, 9)          # the shortcut segment stays behind the taps
+                w2 = conv_k_cmajor(w2, 9)          # the shortcut segment stays behind the taps
                 w[s + ".conv2sc.weight"] = torch.cat([w2, x], dim=1).to(bf).contiguous()
                 w[s + ".conv2sc.bias"] = (self._t(sd, s + ".conv2.bias") + self._t(sd, s + ".conv_shortcut.bias")).contiguous()
                 del w[s + ".conv2.weight"], w[s + ".conv2.bias"]
                 w.pop(s + ".conv2.weight_h", None)
-                if (self.halo and self.halo_sc and halo_level(s) and x.shape[0] % 320 == 0 and w2.shape[1] % (9 * 64) == 0
-                        and x.shape[1] % 64 == 0):
+                if halo_level(s) and x.shape[0] % 320 == 0 and w2.shape[1] % (9 * 64) == 0 and x.shape[1] % 64 == 0:
                     w2h = conv_k_halo32(self._t(sd, s + ".conv2.weight").permute(0, 2, 3, 1).reshape(x.shape[0], -1))
                     w[s + ".conv2sc.weight_h"] = torch.cat([w2h, x], dim=1).to(bf).contiguous()
             norm(t + ".norm1"); convt(t + ".conv1"); norm(t + ".norm2"); convt(t + ".conv2")
@@ -348,19 +311,15 @@ class UNetHIP:
                 w[p + ".net.0.proj.lnfold.weight"] = wgp
                 w[p + ".net.0.proj.lnfold.st"] = torch.stack([wgp.float().sum(dim=1), tp.float()]).contiguous()
             lin(p + ".net.2")
-            if self.ffn_fused and w0.shape == (2 * FFN_HIDDEN, FFN_C):
+            if w0.shape == (2 * FFN_HIDDEN, FFN_C):
                 # operands of wiw_ffn_geglu_bf16: W1 in chunks of [64 value | 64 gate] rows; with the LayerNorm fused, gamma
                 # goes into W1 and beta into b1 (the kernel normalises the raw rows in registers)
                 w1, b1, _ = pack_geglu(w0, b0, FFN_CHUNK)
                 w[p + ".ffn.w1"], w[p + ".ffn.b1"] = TiledW(w1.to(bf).contiguous()), b1.contiguous()
-                if self.ffn32:
-                    w[p + ".ffn32"] = pack_ffn32(w0, b0, self._t(sd, p + ".net.2.weight"), bf)
-                if ln is not None and self.ffn_ln:
+                if ln is not None:
                     gamma, beta = self._t(sd, ln + ".weight"), self._t(sd, ln + ".bias")
                     w1, b1, _ = pack_geglu(w0 * gamma[None, :], w0 @ beta + b0, FFN_CHUNK)
                     w[p + ".ffn.w1ln"], w[p + ".ffn.b1ln"] = TiledW(w1.to(bf).contiguous()), b1.contiguous()
-                    if self.ffn32:
-                        w[p + ".ffn32ln"] = pack_ffn32(w0 * gamma[None, :], w0 @ beta + b0, self._t(sd, p + ".net.2.weight"), bf)
 
         def transformer(p):
             norm(p + ".norm"); lin(p + ".proj_in"); lin(p + ".proj_out")
@@ -437,15 +396,11 @@ class UNetHIP:
         # Every static GEMM weight is re-laid-out for the LDS-DMA stream (hip.TiledW).  Exceptions: `attn1.to_v` of the
         # spatial block is the A operand of a swapped-operand GEMM (V^T = Wv . a^T) and stays row-major; the fused
         # temporal weights are tiled by pack_temporal_qkv.
-        if not os.environ.get("WIW_W_UNTILED"):    # A/B knob
-            for k in list(w):
-                t_ = w[k]
-                if ((k.endswith(".weight") or k.endswith(".weight_h")) and torch.is_tensor(t_) and t_.dim() == 2 and t_.dtype == bf
-                        and t_.shape[1] % 64 == 0 and not k.endswith(".attn1.to_v.weight") and ".fused." not in k):
-                    w[k] = TiledW(t_)
-        for k in list(w):   # the fused FeedForward kernel streams W2 tiled whatever the A/B knob above says
-            if k.endswith(".ffn.w1") and torch.is_tensor(w[k[:-len("ffn.w1")] + "net.2.weight"]):
-                w[k[:-len("ffn.w1")] + "net.2.weight"] = TiledW(w[k[:-len("ffn.w1")] + "net.2.weight"])
+        for k in list(w):
+            t_ = w[k]
+            if ((k.endswith(".weight") or k.endswith(".weight_h")) and torch.is_tensor(t_) and t_.dim() == 2 and t_.dtype == bf
+                    and t_.shape[1] % 64 == 0 and not k.endswith(".attn1.to_v.weight") and ".fused." not in k):
+                w[k] = TiledW(t_)
         # frame-position embeddings depend only on the frame index -> computed once (transformer_temporal.py:329-339)
         T = cfg.num_frames
         self.pos_emb_T: Dict[str, torch.Tensor] = {}
@@ -473,7 +428,7 @@ class UNetHIP:
         convs, FF down-projections) the slab traffic costs more than the idle CUs (+30...+45 %), so those stay whole.
         The factor is decided from the rows of ONE candidate (2 CFG items), never from the batch in flight: a candidate is
         evaluated with the same arithmetic alone and inside any batch (the bit-exact batch contract)."""
-        if self.no_splitk or N % 320 or K < 8192:
+        if N % 320 or K < 8192:
             return 1
         tiles, nk = -(-2 * rows_per_item // 256) * (N // 320), K // 64
         if tiles > 100:
@@ -483,11 +438,9 @@ class UNetHIP:
                 return sk
         return 1
 
-    def _linear(self, x, p, M, *, out_f32=False, silu=False, res1=None, stream=False, **kw):
-        """stream=True: the output is a residual-stream tensor (fp32 when `residual_fp32`)."""
+    def _linear(self, x, p, M, *, out_f32=False, silu=False, res1=None, **kw):
         W = self.w[p + ".weight"]
         N, K = W.shape
-        out_f32 = out_f32 or (stream and self.res32)
         out = self._empty(M, N, dtype=torch.float32 if out_f32 else self.dtype)
         epi = (EPI_OUT_F32 if out_f32 else 0) | (EPI_SILU if silu else 0)
         return self.hip.gemm(x, W, out, M=M, N=N, K=K, C1=K, bias=self.w.get(p + ".bias"), epilogue=epi,
@@ -498,26 +451,20 @@ class UNetHIP:
         h = self._linear(x_bf16, p + ".linear_1", M, silu=True)
         return self._linear(h, p + ".linear_2", M, out_f32=True)
 
-    def _geglu_ff(self, a, p, M, Cn, ln_input=None, stream=True, want16=False, **epi_kw):
+    def _geglu_ff(self, a, p, M, Cn, ln_input=None, f32=False, want16=False, **epi_kw):
         """FeedForward with GEGLU (attention.py:1185-1243): returns GEMM2 output with the given epilogue.
         ln_input: the RAW input of the LayerNorm in front of this FeedForward — given instead of `a` (= None) where the
-        norm is folded into the projection (`_fold_ln`).  stream: the output is a residual-stream tensor (fp32 when
-        `residual_fp32`); False for the AlphaBlender output that only feeds proj_out as an MFMA operand.
-        want16 (fp32 stream only): also return the output's 16-bit rounding -> (out, out16); written by the fused kernel's
-        epilogue at C = 320 (ABI 16), by a cast pass behind the second GEMM elsewhere."""
-        if want16:
-            assert self.res32 and stream
+        norm is folded into the projection (`_fold_ln`, or the fused kernel's in-kernel LayerNorm at C = 320).  f32: the
+        output is an fp32 residual-stream tensor.  want16 (f32 only): also return the output's 16-bit rounding -> (out, out16);
+        written by the fused kernel's epilogue at C = 320 (ABI 16), by a cast pass behind the second GEMM elsewhere."""
+        assert f32 or not want16
         if (p + ".ffn.w1") in self.w:     # C = 320: ONE kernel, the [M, 4C] hidden tensor never exists (ffn.hip)
             ln = ln_input is not None
             assert not ln or (p + ".ffn.w1ln") in self.w
-            out = self._empty(M, Cn, dtype=torch.float32 if (stream and self.res32) else self.dtype)
+            out = self._empty(M, Cn, dtype=torch.float32 if f32 else self.dtype)
             kw = {k: v for k, v in epi_kw.items() if k in ("rowvec", "rowvec_ld", "rows_per_vec", "res1", "ldr1", "beta1",
                                                            "res2", "ldr2", "beta2", "alpha")}
             assert len(kw) == len(epi_kw), f"unsupported FeedForward epilogue arguments: {set(epi_kw) - set(kw)}"
-            if (p + ".ffn32") in self.w and not self.res32:      # opt-in (WIW_FFN32=1): the 32x32x16 form
-                W1s, b1s, W2s = self.w[p + (".ffn32ln" if ln else ".ffn32")]
-                return self.hip.ffn32_geglu(ln_input if ln else a, W1s, b1s, W2s, self.w[p + ".net.2.bias"], out, M, ln=ln,
-                                            ln_eps=1e-5, **kw)
             o16 = self._empty(M, Cn) if want16 else None
             self.hip.ffn_geglu(ln_input if ln else a, self.w[p + (".ffn.w1ln" if ln else ".ffn.w1")],
                                self.w[p + (".ffn.b1ln" if ln else ".ffn.b1")], self.w[p + ".net.2.weight"],
@@ -533,7 +480,6 @@ class UNetHIP:
             self.hip.gemm(a, W1, g, M=M, N=W1.shape[0], K=Cn, C1=Cn, bias=self.w[p + ".net.0.proj.bias"],
                           epilogue=EPI_GEGLU, n_out=4 * Cn)
         W2 = self.w[p + ".net.2.weight"]
-        f32 = stream and self.res32
         out = self._empty(M, Cn, dtype=torch.float32 if f32 else self.dtype)
         self.hip.gemm(g, W2, out, M=M, N=Cn, K=4 * Cn, C1=4 * Cn, bias=self.w[p + ".net.2.bias"],
                       epilogue=EPI_OUT_F32 if f32 else 0, **epi_kw)
@@ -584,71 +530,65 @@ class UNetHIP:
     # ------------------------------------------------------------------------------------------
     # blocks
     # ------------------------------------------------------------------------------------------
-    def _res_block(self, p, x1, C1, x2, C2, Cout, M, H, W, temb_all, eps):
-        """SpatioTemporalResBlock (resnet.py:686-716) on token-major tensors; (x1|x2) is the channel concat."""
+    def _res_block(self, p, x1, C1, x2, C2, Cout, M, H, W, temb_all, eps, ncand=1):
+        """SpatioTemporalResBlock (resnet.py:686-716) on token-major tensors; (x1|x2) is the channel concat.  ncand: the
+        candidates in the batch (`_conv3`).  xs and the block output are block-level stream tensors (`res32_any`)."""
         hip, w, T = self.hip, self.w, self.cfg.num_frames
         S = H * W
         s, t = p + ".spatial_res_block", p + ".temporal_res_block"
         Cin = C1 + C2
-        sdt = self.sdt                       # residual-stream dtype: xs and the block output (fp32 when residual_fp32)
-        epi_s = EPI_OUT_F32 if self.res32 else 0
+        epi_s = EPI_OUT_F32 if self.res32_any else 0
         raw = None
-        if self.res32 and s + ".conv2sc.weight" in w:
+        if self.res32_any and s + ".conv2sc.weight" in w:
             # the fused 1x1 shortcut reads the block input as an MFMA operand: the GroupNorm pass (which holds it in
             # registers anyway) also writes its rounded copy, already concatenated
             raw = self._empty(M, Cin)
         xn = hip.groupnorm(x1, C1, x2, C2, M, S, w[s + ".norm1.weight"], w[s + ".norm1.bias"], eps, True, raw16=raw)
         h = self._empty(M, Cout)
-        self._conv3(xn, s + ".conv1", h, M=M, N=Cout, C=Cin, H=H, W=W, splitk=self._splitk(T * S, Cout, 9 * Cin),
+        self._conv3(xn, s + ".conv1", h, M=M, N=Cout, C=Cin, H=H, W=W, ncand=ncand, splitk=self._splitk(T * S, Cout, 9 * Cin),
                     rowvec=temb_all[:, self.temb_off[s]:], rowvec_ld=self.temb_total, rows_per_vec=S)
         hn = hip.groupnorm(h, Cout, None, 0, M, S, w[s + ".norm2.weight"], w[s + ".norm2.bias"], eps, True)
-        xs = self._empty(M, Cout, dtype=sdt)
+        xs = self._empty(M, Cout, dtype=self.sdt)
         if s + ".conv2sc.weight" in w:     # conv2 + 1x1 shortcut over (x1 | x2) in one implicit GEMM
             sc_ops = dict(A2=raw, C2=Cin) if raw is not None else dict(A2=x1, C2=C1, A3=x2, C3=C2)
-            self._conv3(hn, s + ".conv2sc", xs, M=M, N=Cout, C=Cout, H=H, W=W, splitk=self._splitk(T * S, Cout, 9 * Cout + Cin),
-                        epilogue=epi_s, Ksc=Cin, **sc_ops)
+            self._conv3(hn, s + ".conv2sc", xs, M=M, N=Cout, C=Cout, H=H, W=W, ncand=ncand,
+                        splitk=self._splitk(T * S, Cout, 9 * Cout + Cin), epilogue=epi_s, Ksc=Cin, **sc_ops)
         else:
-            if s + ".conv_shortcut.weight" in w:   # unfused A/B path: separate 1x1 GEMM, then residual
-                assert not self.res32, "WIW_UNFUSED_SHORTCUT is a 16-bit-stream A/B knob"
-                sc = self._empty(M, Cout)
-                hip.gemm(x1, w[s + ".conv_shortcut.weight"], sc, M=M, N=Cout, K=Cin, C1=C1, A2=x2, C2=C2,
-                         bias=w[s + ".conv_shortcut.bias"])
-            else:
-                assert x2 is None
-                sc = x1
-            self._conv3(hn, s + ".conv2", xs, M=M, N=Cout, C=Cout, H=H, W=W, splitk=self._splitk(T * S, Cout, 9 * Cout),
-                        res1=sc, ldr1=Cout, beta1=1.0, epilogue=epi_s)
+            assert x2 is None
+            self._conv3(hn, s + ".conv2", xs, M=M, N=Cout, C=Cout, H=H, W=W, ncand=ncand,
+                        splitk=self._splitk(T * S, Cout, 9 * Cout), res1=x1, ldr1=Cout, beta1=1.0, epilogue=epi_s)
         # temporal resnet: GroupNorm statistics run over (T, H, W) of each batch item (5-D input, resnet.py:611)
         xn = hip.groupnorm(xs, Cout, None, 0, M, T * S, w[t + ".norm1.weight"], w[t + ".norm1.bias"], eps, True, clip=True)
         hip.gemm(xn, w[t + ".conv1.weight"], h, M=M, N=Cout, K=3 * Cout, C1=Cout, mode=A_CONV_T3, H=H, Wd=W, T=T,
                  bias=w[t + ".conv1.bias"], rowvec=temb_all[:, self.temb_off[t]:], rowvec_ld=self.temb_total,
-                 rows_per_vec=S, epilogue=self.kc)
+                 rows_per_vec=S, epilogue=K_CMAJOR)
         hn = hip.groupnorm(h, Cout, None, 0, M, T * S, w[t + ".norm2.weight"], w[t + ".norm2.bias"], eps, True, out=hn, clip=True)
         a = self.alpha[p]
-        out = self._empty(M, Cout, dtype=sdt)
+        out = self._empty(M, Cout, dtype=self.sdt)
         # AlphaBlender: a*xs + (1-a)*(xs + conv2(h) + b) = xs + (1-a)*(acc + b)   (resnet.py:784-797)
         hip.gemm(hn, w[t + ".conv2.weight"], out, M=M, N=Cout, K=3 * Cout, C1=Cout, mode=A_CONV_T3, H=H, Wd=W, T=T,
-                 bias=w[t + ".conv2.bias"], alpha=1.0 - a, res1=xs, ldr1=Cout, beta1=1.0, epilogue=epi_s | self.kc)
+                 bias=w[t + ".conv2.bias"], alpha=1.0 - a, res1=xs, ldr1=Cout, beta1=1.0, epilogue=epi_s | K_CMAJOR)
         return out
 
-    def _conv3(self, x, key, out, *, M, N, C, H, W, splitk=1, epilogue=0, Ksc=0, mode=A_CONV3X3, **kw):
+    def _conv3(self, x, key, out, *, M, N, C, H, W, ncand, splitk=1, epilogue=0, Ksc=0, mode=A_CONV3X3, **kw):
         """One 3x3 convolution (stride 1, pad 1; Ksc > 0: + the fused 1x1 shortcut segment over A2 | A3 in `kw`; mode
         A_CONV3X3_UP: behind a nearest x2 upsample, H x W the OUTPUT size) as an implicit GEMM: the halo-staged kernel (weight
         copy `key.weight_h`, WIW_K_HALO32) when the geometry and the epilogue fit it, else the per-tap kernels on `key.weight`."""
         w = self.w
         wh = w.get(key + ".weight_h")
         # The two kernels sum K in different orders, so WHICH one runs must not depend on the batch in flight: the geometry
-        # test is made on the rows of ONE candidate as well (18 x 32 frames straddle tiles: 28 CFG frames of a candidate are
-        # 63 whole tiles, the 14 frames of a candidate without CFG are not — then every batch size takes the per-tap kernel)
+        # test is made on the rows of ONE of the `ncand` candidates as well (18 x 32 frames straddle tiles: 28 CFG frames of a
+        # candidate are 63 whole tiles, the 14 frames of a candidate without CFG are not — then every batch size takes the
+        # per-tap kernel)
         up = mode == A_CONV3X3_UP
-        if (wh is not None and splitk <= 1 and not (epilogue & ~EPI_OUT_F32) and isinstance(wh, TiledW)
+        if (wh is not None and splitk <= 1 and not (epilogue & ~EPI_OUT_F32)
                 and self.hip.conv_halo_ok(M, N, C, H, W, up=up)
-                and self.hip.conv_halo_ok(M // max(getattr(self, "_ncand", 1), 1), N, C, H, W, up=up)):
+                and self.hip.conv_halo_ok(M // ncand, N, C, H, W, up=up)):
             self.hip.gemm(x, wh, out, M=M, N=N, K=9 * C + Ksc, C1=C, mode=mode, H=H, Wd=W, bias=w[key + ".bias"],
                           epilogue=K_HALO32 | epilogue, **kw)
         else:
             self.hip.gemm(x, w[key + ".weight"], out, M=M, N=N, K=9 * C + Ksc, C1=C, mode=mode, H=H, Wd=W,
-                          bias=w[key + ".bias"], splitk=splitk, epilogue=epilogue | self.kc, **kw)
+                          bias=w[key + ".bias"], splitk=splitk, epilogue=epilogue | K_CMAJOR, **kw)
 
     def _cross_attention(self, q, h, M, Cn, rows_per_item, heads, cond: RequestCond):
         """x + attn2(norm2(x), tokens) with P > 1 conditioning tokens (attention.py:545-551 / 740-743): LayerNorm, Q projection,
@@ -656,43 +596,31 @@ class UNetHIP:
         item are consecutive in this build's token order for the spatial AND the temporal block (its time_context is the
         first frame's tokens = the item's, transformer_temporal.py:313-320), so both use rows_per_item = T * S."""
         hip, w = self.hip, self.w
-        if self.legacy_cross_guard:
-            raise NotImplementedError("WIW_LN_ADDVEC (A/B knob of the single-key closed form) with num_past_obs > 1")
         a2 = hip.layernorm(h, M, Cn, w[q + ".norm2.weight"], w[q + ".norm2.bias"])
         q2 = self._linear(a2, q + ".attn2.to_q", M)
         K, V = cond.cross_kv[q]
         o2 = hip.cross_attn_fewkeys(q2, Cn, K, V, a2, Cn, M, rows_per_item, heads, cond.P, 1.0 / math.sqrt(64.0))
-        return self._linear(o2, q + ".attn2.to_out.0", M, res1=h, stream=h.dtype == torch.float32)   # stays on h's stream
+        return self._linear(o2, q + ".attn2.to_out.0", M, res1=h, out_f32=h.dtype == torch.float32)   # stays on h's stream
 
     def _transformer(self, p, x, Cn, M, H, W, heads, cond: RequestCond):
-        """TransformerSpatioTemporalModel (transformer_temporal.py:279-382), one layer."""
-        rb = self.res32
-        self.res32 = self.res32_tr            # the hidden stream between proj_in and proj_out
-        try:
-            hb = self._transformer_inside(p, x, Cn, M, H, W, heads, cond)
-        finally:
-            self.res32 = rb
-        return self._linear(hb, p + ".proj_out", M, res1=x, stream=True)      # back on the block-level stream
-
-    def _transformer_inside(self, p, x, Cn, M, H, W, heads, cond: RequestCond):
+        """TransformerSpatioTemporalModel (transformer_temporal.py:279-382), one layer.  x is a block-level stream tensor
+        (`res32_any`); the hidden stream between proj_in and proj_out is fp32 only with `res32_tr`."""
         hip, w, T = self.hip, self.w, self.cfg.num_frames
+        f32 = self.res32_tr
         S = H * W
         frames = M // S
         batch = frames // T
         b, t = p + ".transformer_blocks.0", p + ".temporal_transformer_blocks.0"
         scale = 1.0 / math.sqrt(64.0)
         xn = hip.groupnorm(x, Cn, None, 0, M, S, w[p + ".norm.weight"], w[p + ".norm.bias"], 1e-6, False)
-        tb = lambda k: bool((self.tr_mask >> k) & 1)      # noqa: E731  (is hidden-stream tensor k fp32?)
-        h = self._linear(xn, p + ".proj_in", M, stream=tb(0))
+        h = self._linear(xn, p + ".proj_in", M, out_f32=f32)
         # ---- spatial block (attention.py:462-582)
-        legacy = bool(os.environ.get("WIW_LN_ADDVEC"))   # A/B knob: the adds inside the LayerNorm kernel (extra write pass)
-        # LayerNorm folded into its consumer GEMM where that GEMM runs on the 256x160 tile (`_fold_ln`): the projection
-        # reads the RAW residual stream, the kernel derives mean / rstd of its rows from the operand fragments
+        # LayerNorm folded into its consumer GEMM where that GEMM runs on the 256x160 tile (`_fold_ln`; at C = 320 the fused
+        # FeedForward normalises in-kernel): the projection reads the RAW residual stream, the kernel derives mean / rstd
+        # of its rows from the operand fragments
         fold_qkv = (b + ".attn1.to_qkv.lnfold.weight") in w
-        fold_ff = ((b + ".ff.net.0.proj.lnfold.weight") in w or (b + ".ff.ffn.w1ln") in w) and not legacy
+        fold_ff = (b + ".ff.net.0.proj.lnfold.weight") in w or (b + ".ff.ffn.w1ln") in w
         a = xn
-        if self.res32:
-            assert not (fold_qkv or legacy), "A/B knobs of the 16-bit stream"
         if not fold_qkv:
             a = hip.layernorm(h, M, Cn, w[b + ".norm1.weight"], w[b + ".norm1.bias"], out=xn)
         Sv = -(-S // 8) * 8      # V^T frame stride: S, or the next multiple of 8 (frame-padded V^T, any latent size)
@@ -714,42 +642,36 @@ class UNetHIP:
         # The adds that follow a GEMM in the reference — the single-key cross-attention output (one vector per CFG item,
         # attention.py:545-551, 740-743) and the frame-position embedding (transformer_temporal.py:352-353) — ride in that
         # GEMM's epilogue as its per-row-group vector, so every LayerNorm below is a plain one-read / one-write pass.
-        if legacy:
-            h = self._linear(o, b + ".attn1.to_out.0", M, res1=h)
-            a = hip.layernorm(h, M, Cn, w[b + ".norm3.weight"], w[b + ".norm3.bias"], addvec=cond.cross[b], addvec_ld=Cn,
-                              rows_per_vec=T * S, sum_out=h, out=a)
-        elif cond.P > 1:
-            h = self._linear(o, b + ".attn1.to_out.0", M, res1=h, stream=tb(1))
+        if cond.P > 1:
+            h = self._linear(o, b + ".attn1.to_out.0", M, res1=h, out_f32=f32)
             h = self._cross_attention(b, h, M, Cn, T * S, heads, cond)
-            if not fold_ff:
-                a = hip.layernorm(h, M, Cn, w[b + ".norm3.weight"], w[b + ".norm3.bias"], out=a)
         else:
             h = self._linear(o, b + ".attn1.to_out.0", M, res1=h, rowvec=cond.cross[b], rowvec_ld=Cn, rows_per_vec=T * S,
-                             stream=tb(1))
-            if not fold_ff:
-                a = hip.layernorm(h, M, Cn, w[b + ".norm3.weight"], w[b + ".norm3.bias"], out=a)
+                             out_f32=f32)
+        if not fold_ff:
+            a = hip.layernorm(h, M, Cn, w[b + ".norm3.weight"], w[b + ".norm3.bias"], out=a)
         am = self.alpha[p]
         # hs + emb is stored instead of hs; the blend below subtracts am * emb again
-        fold_emb = abs(1.0 - am) > 1e-4 and not legacy
-        if self.res32 and not fold_emb:
+        fold_emb = abs(1.0 - am) > 1e-4
+        if f32 and not fold_emb:
             raise NotImplementedError("residual_fp32 with sigmoid(mix_factor) == 1: the pre-add LayerNorm path is 16-bit only")
         lnin = h if fold_ff else None         # the FeedForwards below take the RAW stream where their norm is folded
         if fold_emb:
             hm = self._geglu_ff(a, b + ".ff", M, Cn, ln_input=lnin, res1=h, ldr1=Cn, beta1=1.0, rowvec=cond.pos_emb[p],
-                                rowvec_ld=Cn, rows_per_vec=S, stream=tb(2))
+                                rowvec_ld=Cn, rows_per_vec=S, f32=f32)
             hs = hm                           # = spatial output + emb
             if not fold_ff:
                 a = hip.layernorm(hm, M, Cn, w[t + ".norm_in.weight"], w[t + ".norm_in.bias"], out=a)
         else:
-            hs = self._geglu_ff(a, b + ".ff", M, Cn, ln_input=lnin, res1=h, ldr1=Cn, beta1=1.0, stream=tb(2))
+            hs = self._geglu_ff(a, b + ".ff", M, Cn, ln_input=lnin, res1=h, ldr1=Cn, beta1=1.0, f32=f32)
             hm = self._empty(M, Cn)
             a = hip.layernorm(hs, M, Cn, w[t + ".norm_in.weight"], w[t + ".norm_in.bias"], addvec=cond.pos_emb[p],
                               addvec_ld=Cn, rows_per_vec=S, sum_out=hm, out=a)
         # ---- temporal block (attention.py:707-762); rows stay in (b,t,s) order
-        t_fused = T <= 14 and not self.temporal_unfused and M * Cn * 2 < (1 << 32)
-        w16 = tb(3) and t_fused               # ff_in's output is fp32 and the fused temporal block wants its 16-bit rounding
+        t_fused = T <= 14 and M * Cn * 2 < (1 << 32)      # else the unfused form below: the fused kernel's shape limits
+        w16 = f32 and t_fused                 # ff_in's output is fp32 and the fused temporal block wants its 16-bit rounding
         hm = self._geglu_ff(a, t + ".ff_in", M, Cn, ln_input=hm if (fold_ff and fold_emb) else None, res1=hm, ldr1=Cn, beta1=1.0,
-                            stream=tb(3), want16=w16)
+                            f32=f32, want16=w16)
         if t_fused:
             # norm1 + to_q/k/v + the 14x14 attention in ONE kernel (temporal.hip): LayerNorm folded into the projection,
             # Q/K/V never leave the registers — no LayerNorm pass, no 3C-wide QKV tensor.  (fp32 stream: the kernel reads the
@@ -762,31 +684,21 @@ class UNetHIP:
             qkv = self._empty(M, 3 * Cn)
             hip.gemm(a, w[t + ".attn1.to_qkv.weight"], qkv, M=M, N=3 * Cn, K=Cn, C1=Cn)
             hip.attn_temporal(qkv, 3 * Cn, o, Cn, batch, T, S, heads, scale)
-        if legacy:
-            hm = self._linear(o, t + ".attn1.to_out.0", M, res1=hm)
-            a = hip.layernorm(hm, M, Cn, w[t + ".norm3.weight"], w[t + ".norm3.bias"], addvec=cond.cross[t], addvec_ld=Cn,
-                              rows_per_vec=T * S, sum_out=hm, out=a)
-        elif cond.P > 1:
-            hm = self._linear(o, t + ".attn1.to_out.0", M, res1=hm, stream=tb(4))
+        if cond.P > 1:
+            hm = self._linear(o, t + ".attn1.to_out.0", M, res1=hm, out_f32=f32)
             hm = self._cross_attention(t, hm, M, Cn, T * S, heads, cond)
-            if not fold_ff:
-                a = hip.layernorm(hm, M, Cn, w[t + ".norm3.weight"], w[t + ".norm3.bias"], out=a)
         else:
             hm = self._linear(o, t + ".attn1.to_out.0", M, res1=hm, rowvec=cond.cross[t], rowvec_ld=Cn, rows_per_vec=T * S,
-                              stream=tb(4))
-            if not fold_ff:
-                a = hip.layernorm(hm, M, Cn, w[t + ".norm3.weight"], w[t + ".norm3.bias"], out=a)
+                              out_f32=f32)
+        if not fold_ff:
+            a = hip.layernorm(hm, M, Cn, w[t + ".norm3.weight"], w[t + ".norm3.bias"], out=a)
         # AlphaBlender: am*hs + (1-am)*(hm + ff(a)); with hs' = hs + emb stored: am*hs = am*hs' - am*emb, and the
         # epilogue's vector enters as alpha * rowvec with alpha = 1 - am  ->  rowvec = -am / (1 - am) * emb
-        lnin = hm if fold_ff else None
         # (the blend only feeds proj_out as an MFMA operand: 16-bit in both stream modes)
-        if fold_emb:
-            hb = self._geglu_ff(a, t + ".ff", M, Cn, ln_input=lnin, alpha=1.0 - am, res1=hm, ldr1=Cn, beta1=1.0 - am, res2=hs,
-                                ldr2=Cn, beta2=am, rowvec=cond.pos_emb_blend[p], rowvec_ld=Cn, rows_per_vec=S, stream=False)
-        else:
-            hb = self._geglu_ff(a, t + ".ff", M, Cn, ln_input=lnin, alpha=1.0 - am, res1=hm, ldr1=Cn, beta1=1.0 - am, res2=hs,
-                                ldr2=Cn, beta2=am, stream=False)
-        return hb
+        blend_emb = dict(rowvec=cond.pos_emb_blend[p], rowvec_ld=Cn, rows_per_vec=S) if fold_emb else {}
+        hb = self._geglu_ff(a, t + ".ff", M, Cn, ln_input=hm if fold_ff else None, alpha=1.0 - am, res1=hm, ldr1=Cn,
+                            beta1=1.0 - am, res2=hs, ldr2=Cn, beta2=am, **blend_emb)
+        return self._linear(hb, p + ".proj_out", M, res1=x, out_f32=self.res32_any)      # back on the block-level stream
 
     # ------------------------------------------------------------------------------------------
     # forward
@@ -811,13 +723,14 @@ class UNetHIP:
         frames = cond.Bc * T
         M = frames * h * w_
         assert x_in.shape == (M, CIN_PAD) and (h % (1 << (n - 1)) == 0) and (w_ % (1 << (n - 1)) == 0)
-        self._ncand = cond.B        # `_conv3` decides from ONE candidate's rows (the bit-exact batch contract)
         temb_all = self._empty(frames, self.temb_total, dtype=torch.float32)
         hip.gemm(emb_silu, w["temb_all.weight"], temb_all, M=frames, N=self.temb_total, K=cfg.time_embed_dim,
                  C1=cfg.time_embed_dim, bias=w["temb_all.bias"], epilogue=EPI_OUT_F32)
-        epi_s = EPI_OUT_F32 if self.res32 else 0     # residual-stream outputs (fp32 when residual_fp32)
+        f32 = self.res32_any
+        epi_s = EPI_OUT_F32 if f32 else 0     # block-level residual-stream outputs
         x = self._empty(M, ch[0], dtype=self.sdt)
-        self._conv3(x_in, "conv_in", x, M=M, N=ch[0], C=CIN_PAD, H=h, W=w_, epilogue=epi_s)
+        # `_conv3` decides from ONE candidate's rows (the bit-exact batch contract)
+        self._conv3(x_in, "conv_in", x, M=M, N=ch[0], C=CIN_PAD, H=h, W=w_, ncand=cond.B, epilogue=epi_s)
         skips = [(x, ch[0])]
         H, W, C = h, w_, ch[0]
         for i in range(n):
@@ -825,7 +738,7 @@ class UNetHIP:
             has_attn = i < n - 1
             eps = 1e-6 if has_attn else 1e-5
             for j in range(L):
-                x = self._res_block(f"{p}.resnets.{j}", x, C, None, 0, ch[i], M, H, W, temb_all, eps)
+                x = self._res_block(f"{p}.resnets.{j}", x, C, None, 0, ch[i], M, H, W, temb_all, eps, cond.B)
                 C = ch[i]
                 if has_attn:
                     x = self._transformer(f"{p}.attentions.{j}", x, C, M, H, W, cfg.num_attention_heads[i], cond)
@@ -835,20 +748,20 @@ class UNetHIP:
                 y = self._empty(M, C, dtype=self.sdt)
                 q = f"{p}.downsamplers.0.conv"
                 # (an fp32 stream enters the convolution as its rounded copy: Downsample2D has no norm in front of it)
-                hip.gemm(hip.cast16(x) if self.res32 else x, w[q + ".weight"], y, M=M, N=C, K=9 * C, C1=C, mode=A_CONV3X3_S2,
-                         H=H, Wd=W, bias=w[q + ".bias"], epilogue=epi_s | self.kc)
+                hip.gemm(hip.cast16(x) if f32 else x, w[q + ".weight"], y, M=M, N=C, K=9 * C, C1=C, mode=A_CONV3X3_S2,
+                         H=H, Wd=W, bias=w[q + ".bias"], epilogue=epi_s | K_CMAJOR)
                 x = y
                 skips.append((x, C))
-        x = self._res_block("mid_block.resnets.0", x, C, None, 0, C, M, H, W, temb_all, 1e-5)
+        x = self._res_block("mid_block.resnets.0", x, C, None, 0, C, M, H, W, temb_all, 1e-5, cond.B)
         x = self._transformer("mid_block.attentions.0", x, C, M, H, W, cfg.num_attention_heads[-1], cond)
-        x = self._res_block("mid_block.resnets.1", x, C, None, 0, C, M, H, W, temb_all, 1e-5)
+        x = self._res_block("mid_block.resnets.1", x, C, None, 0, C, M, H, W, temb_all, 1e-5, cond.B)
         rch = list(reversed(ch))
         rheads = list(reversed(cfg.num_attention_heads))
         for i in range(n):
             p = f"up_blocks.{i}"
             for j in range(L + 1):
                 sk, Cs = skips.pop()
-                x = self._res_block(f"{p}.resnets.{j}", x, C, sk, Cs, rch[i], M, H, W, temb_all, 1e-6)
+                x = self._res_block(f"{p}.resnets.{j}", x, C, sk, Cs, rch[i], M, H, W, temb_all, 1e-6, cond.B)
                 C = rch[i]
                 if i > 0:
                     x = self._transformer(f"{p}.attentions.{j}", x, C, M, H, W, rheads[i], cond)
@@ -856,12 +769,13 @@ class UNetHIP:
                 H, W, M = H * 2, W * 2, M * 4
                 y = self._empty(M, C, dtype=self.sdt)
                 q = f"{p}.upsamplers.0.conv"
-                self._conv3(hip.cast16(x) if self.res32 else x, q, y, M=M, N=C, C=C, H=H, W=W, epilogue=epi_s, mode=A_CONV3X3_UP)
+                self._conv3(hip.cast16(x) if f32 else x, q, y, M=M, N=C, C=C, H=H, W=W, ncand=cond.B, epilogue=epi_s,
+                            mode=A_CONV3X3_UP)
                 x = y
         xn = hip.groupnorm(x, C, None, 0, M, H * W, w["conv_norm_out.weight"], w["conv_norm_out.bias"], 1e-5, True)
         out = self._empty(M, cfg.out_channels, dtype=torch.float32)
         hip.gemm(xn, w["conv_out.weight"], out, M=M, N=cfg.out_channels, K=9 * C, C1=C, mode=A_CONV3X3, H=H, Wd=W,
-                 bias=w["conv_out.bias"], epilogue=EPI_OUT_F32 | self.kc)
+                 bias=w["conv_out.bias"], epilogue=EPI_OUT_F32 | K_CMAJOR)
         return out
 
     # ------------------------------------------------------------------------------------------

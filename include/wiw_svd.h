@@ -52,7 +52,9 @@ extern "C" {
                                 15: wiw_groupnorm_onepass / wiw_groupnorm_onepass_ok (one-pass GroupNorm of the inner levels);
                              16: wiw_ffn_geglu_f32stream2 (the fused FeedForward's LayerNorm reads the fp32 stream; a second,
                                  16-bit output); wiw_cross_attn_fewkeys_bf16 (cross-attention over 2..8 conditioning tokens);
-                             17: wiw_calib_mfma_random (the box calibration loop on random operands: the SUSTAINED matrix-pipe rate) */
+                             17: wiw_calib_mfma_random (the box calibration loop on random operands: the SUSTAINED matrix-pipe rate);
+                                 added since, without a version step: wiw_attn_spatial_ps_padded_bf16 / wiw_transpose_framepad_bf16,
+                                 wiw_grad_sumsq_chunk / wiw_grad_sumsq_partials / wiw_grad_norm_finalize / wiw_adamw_step_scaled */
 
 int wiw_abi_version(void);
 
@@ -486,6 +488,28 @@ int wiw_adamw_step(void* stream, float* p, const float* g, float* m, float* v, v
                    float beta2, float eps, float weight_decay, int step);
 int wiw_edm_loss_grad(void* stream, const float* pred, const float* noisy, const float* target, int64_t n, float sigma,
                       float* grad, float* partial, int n_partial);
+/* Global-norm gradient clipping (the `gradient_clipping` of the reference's DeepSpeed configs, FTsvd/config/
+ * accelerate_deepspeed_o*_config.yaml; the coefficient of torch.nn.utils.clip_grad_norm_).  Added at ABI 17, additively.
+ * wiw_grad_sumsq_partials: the sums of squares of MANY fp32 tensors in ONE launch.  table: n_tensors rows of three 64-bit
+ *   words in device memory — (address, element count, index of the tensor's first chunk); a tensor of n elements owns
+ *   ceil(n / L) consecutive chunks of L = wiw_grad_sumsq_chunk() elements, n_chunks is their total, partial[c] receives the
+ *   sum of squares of chunk c.  Addresses need 4-byte alignment only (16-byte loads on the aligned body, scalar head and
+ *   tail); counts and offsets are 64-bit.  Which elements feed a partial and in which (pairwise) order they are added
+ *   depends on the table alone, NOT on `blocks` (0: sized by the library; blocks walk the chunks grid-stride): the
+ *   result is bit-repeatable.  No atomics.  Inf / NaN inputs give a non-finite partial.  Relative error of a partial
+ *   <= (log2(L) + 2) 2^-24.
+ * wiw_grad_norm_finalize: ONE block.  partial != NULL: out[0] = sumsq = the partials added in index order in double
+ *   precision.  partial == NULL: out[0] is taken as given (e.g. the all-reduced sum over the ranks of a sharded
+ *   optimiser).  Then, if max_norm > 0: out[1] = norm = sqrt(sumsq), out[2] = coef = min(1, max_norm / (norm + 1e-6))
+ *   (NaN stays NaN), out[3] = 1.0 if sumsq is finite else 0.0.  max_norm <= 0 with partials: the sum only.
+ * wiw_adamw_step_scaled: wiw_adamw_step with every gradient element multiplied by *gscale (device memory, e.g. out + 2
+ *   above) as it is loaded; the product is rounded to fp32 before use, so *gscale == 1 reproduces wiw_adamw_step's bits and
+ *   a scale s reproduces wiw_adamw_step on a gradient pre-multiplied by s in fp32.  `g` is not written. */
+int wiw_grad_sumsq_chunk(void);
+int wiw_grad_sumsq_partials(void* stream, const void* table, int n_tensors, int64_t n_chunks, float* partial, int blocks);
+int wiw_grad_norm_finalize(void* stream, const float* partial, int64_t n_partial, float max_norm, float* out);
+int wiw_adamw_step_scaled(void* stream, float* p, const float* g, float* m, float* v, void* p16, int64_t n, float lr, float beta1,
+                          float beta2, float eps, float weight_decay, int step, const float* gscale);
 /* wiw_ema_step_f32: `EMAModel.step` of `--use_ema` (dp/training_utils.py:425-472, train_svd.py:979-980) on a flat fp32 range:
  *   shadow -= one_minus_decay * (shadow - param), the three fp32 operations in that order (bit-identical to the reference's
  *   `s_param.sub_(one_minus_decay * (s_param - param))`).  Pointers 16-byte aligned. */

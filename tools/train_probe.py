@@ -1,6 +1,11 @@
 """Where one fine-tuning step goes, by OPERATOR (not by kernel): HIP-event time of every backward closure of the tape, summed
 per operator kind, plus the linear / conv backward split into dx | weight-gradient | bias pieces, and a sweep of the
-weight-gradient GEMM over orientation (dW vs dW^T) and split-K factors at the served shapes.  GPU box only."""
+weight-gradient GEMM over orientation (dW vs dW^T) and split-K factors at the served shapes.  GPU box only.
+
+`--max_grad_norm C` instead measures what global-norm gradient clipping costs: the whole `Trainer.step` (PH x PW x 14, default
+576 x 1024) without and with the threshold, in one process on one box, in alternating blocks (off, on, off, on), plus the
+norm kernels on their own (ms and GB/s over the trainer's own gradient tensors)."""
+import argparse
 import collections
 import os
 import sys
@@ -156,7 +161,59 @@ def wgrad_sweep():
         del dyT, xT, out, outT
 
 
+def clip_cost(max_grad_norm: float, steps: int = 5, dtype=torch.bfloat16):
+    import json
+    import statistics
+
+    from wiw_amd.train_unet import Trainer
+
+    cfg = UNetConfig()
+    net = UNetTrain(cfg, random_state_dict_torch(cfg, 0, dev, torch.float32), dev, dtype=dtype)
+    gen = torch.Generator().manual_seed(100)
+    Tn, h, w = 14, H // 8, W // 8
+    lat, noise = torch.randn(1, Tn, 4, h, w, generator=gen) * 0.8, torch.randn(1, Tn, 4, h, w, generator=gen)
+    st = T.prepare_step(lat, noise, 1.3, torch.randn(1, 4, h, w, generator=gen), torch.randn(1, 1, 1024, generator=gen), 0.04,
+                        torch.zeros(1, Tn, 14))
+    tr = Trainer(net, lr=1e-5, autotune=True)
+    for _ in range(2):                                   # warm-up: weight-gradient plans, allocator
+        tr.step(st)
+    tr.max_grad_norm = max_grad_norm
+    tr.step(st)                                          # ... and the norm's table / partial buffers
+    torch.cuda.synchronize()
+    blocks = []
+    for setting in (None, max_grad_norm, None, max_grad_norm):
+        tr.max_grad_norm = setting
+        ms = []
+        for _ in range(steps):
+            torch.cuda.synchronize(); t0 = time.perf_counter()
+            tr.step(st)
+            torch.cuda.synchronize(); ms.append(1e3 * (time.perf_counter() - t0))
+        blocks.append({"max_grad_norm": setting, "ms_per_step_median": round(statistics.median(ms), 2), "ms_per_step_all": [round(x, 1) for x in ms],
+                       "grad_norm": tr.grad_norm if setting is not None else None})
+    off = statistics.median(x for b in blocks if b["max_grad_norm"] is None for x in b["ms_per_step_all"])
+    on = statistics.median(x for b in blocks if b["max_grad_norm"] is not None for x in b["ms_per_step_all"])
+    # the norm kernels alone, over the gradient tensors the last step left (HIP events around 20 calls; the table is cached)
+    flat = [g.reshape(-1).contiguous() for n, g in net.grads.items() if tr.trainable(n)]
+    nbytes = 4.0 * sum(t.numel() for t in flat)
+    up0 = net.hip.sumsq_table_uploads
+    ms_norm = timeit(lambda: net.hip.grad_sumsq(flat, max_grad_norm), 20)
+    print(json.dumps({"probe": "clip_cost", "size": f"{H}x{W}x{Tn}", "dtype": str(dtype), "blocks": blocks,
+                      "ms_per_step_off": round(off, 2), "ms_per_step_on": round(on, 2), "on_over_off": round(on / off, 4),
+                      "norm_tensors": len(flat), "norm_GB": round(nbytes / 1e9, 3), "norm_ms": round(ms_norm, 4),
+                      "norm_GBps": round(nbytes / ms_norm / 1e6, 1), "table_uploads_in_21_calls": net.hip.sumsq_table_uploads - up0,
+                      "table_uploads_total": net.hip.sumsq_table_uploads}))
+
+
 if __name__ == "__main__":
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--max_grad_norm", type=float, default=None, help="measure the cost of global-norm gradient clipping at this "
+                    "threshold (the reference's DeepSpeed config uses 0.5) instead of the operator / sweep probes")
+    ap.add_argument("--steps", type=int, default=5, help="--max_grad_norm: timed steps per block")
+    ap.add_argument("--dtype", choices=["bf16", "fp16"], default="bf16")
+    args = ap.parse_args()
+    if args.max_grad_norm is not None:
+        clip_cost(args.max_grad_norm, args.steps, torch.float16 if args.dtype == "fp16" else torch.bfloat16)
+        sys.exit(0)
     if os.environ.get("ONLY", "") != "sweep":
         step_by_operator()
     if os.environ.get("ONLY", "") != "ops":

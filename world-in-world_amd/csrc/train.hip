@@ -15,16 +15,30 @@ namespace {
 //   p <- p - lr * (m / bc1) / (sqrt(v / bc2) + eps)          bc1 = 1 - b1^step, bc2 = 1 - b2^step
 // and the 16-bit copy the forward / backward GEMMs read is refreshed in the same pass (24 B of HBM traffic per
 // parameter + 2 B for the copy: the update of the 1.53 B-parameter UNet is ~40 GB, HBM-bound).
+// SCALED (wiw_adamw_step_scaled, gradient clipping): every gradient element is multiplied by *gscale as it is loaded — the clipped
+// gradient never goes to memory and the host never needs the norm.  The product is ROUNDED before the moment updates use it
+// (scaled_grad), so the result equals the plain kernel's on a gradient pre-multiplied in fp32, and its bits when *gscale == 1.
+template <bool SCALED>
+WIW_DEV float scaled_grad(float g, float s) {
+    if (!SCALED) return g;
+    float r = g * s;
+    asm volatile("" : "+v"(r));   // no fma contraction of this product into the moment updates (as ema_one below)
+    return r;
+}
+template <bool SCALED>
 __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                      float* __restrict__ v, uint16_t* __restrict__ p16, int64_t n, float lr,
-                                                     float b1, float b2, float eps, float wd, float inv_bc1, float inv_sqrt_bc2) {
+                                                     float b1, float b2, float eps, float wd, float inv_bc1, float inv_sqrt_bc2,
+                                                     const float* __restrict__ gscale) {
     const int64_t stride = (int64_t)gridDim.x * 256 * 4;
+    const float gs = SCALED ? *gscale : 1.0f;
     for (int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4; i < n; i += stride) {
         if (i + 4 <= n) {
             float4 pp = *(const float4*)(p + i), mm = *(const float4*)(m + i), vv = *(const float4*)(v + i);
             const float4 gg = *(const float4*)(g + i);
             float pa[4] = {pp.x, pp.y, pp.z, pp.w}, ma[4] = {mm.x, mm.y, mm.z, mm.w}, va[4] = {vv.x, vv.y, vv.z, vv.w};
-            const float ga[4] = {gg.x, gg.y, gg.z, gg.w};
+            const float ga[4] = {scaled_grad<SCALED>(gg.x, gs), scaled_grad<SCALED>(gg.y, gs), scaled_grad<SCALED>(gg.z, gs),
+                                 scaled_grad<SCALED>(gg.w, gs)};
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 pa[e] *= 1.0f - lr * wd;
@@ -44,8 +58,9 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const
         } else {
             for (int64_t j = i; j < n; ++j) {
                 float pj = p[j] * (1.0f - lr * wd);
-                const float mj = b1 * m[j] + (1.0f - b1) * g[j];
-                const float vj = b2 * v[j] + (1.0f - b2) * g[j] * g[j];
+                const float gj = scaled_grad<SCALED>(g[j], gs);
+                const float mj = b1 * m[j] + (1.0f - b1) * gj;
+                const float vj = b2 * v[j] + (1.0f - b2) * gj * gj;
                 pj -= lr * (mj * inv_bc1) / (sqrtf(vj) * inv_sqrt_bc2 + eps);
                 p[j] = pj; m[j] = mj; v[j] = vj;
                 if (p16) p16[j] = f2bf(pj);
@@ -1415,8 +1430,8 @@ extern "C" int wiw_ema_step_f32(void* stream, float* shadow, const float* param,
     return wiw_check_launch("wiw_ema_step_f32");
 }
 
-extern "C" int wiw_adamw_step(void* stream, float* p, const float* g, float* m, float* v, void* p16, int64_t n, float lr,
-                              float beta1, float beta2, float eps, float weight_decay, int step) {
+static int adamw_launch(void* stream, float* p, const float* g, float* m, float* v, void* p16, int64_t n, float lr, float beta1,
+                        float beta2, float eps, float weight_decay, int step, const float* gscale, const char* what) {
     WIW_REQUIRE(p && g && m && v, "adamw: null pointer");
     WIW_REQUIRE(n > 0 && step >= 1, "adamw: n > 0 and step >= 1");
     WIW_REQUIRE(((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0) && ((((uintptr_t)p16) & 7) == 0),
@@ -1424,9 +1439,149 @@ extern "C" int wiw_adamw_step(void* stream, float* p, const float* g, float* m, 
     const float bc1 = 1.0f - powf(beta1, (float)step), bc2 = 1.0f - powf(beta2, (float)step);
     int64_t blocks = (n + 1023) / 1024;
     if (blocks > 256 * 16) blocks = 256 * 16;
-    hipLaunchKernelGGL(adamw_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (uint16_t*)p16, n, lr,
-                       beta1, beta2, eps, weight_decay, 1.0f / bc1, 1.0f / sqrtf(bc2));
-    return wiw_check_launch("wiw_adamw_step");
+    if (gscale)
+        hipLaunchKernelGGL(adamw_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (uint16_t*)p16,
+                           n, lr, beta1, beta2, eps, weight_decay, 1.0f / bc1, 1.0f / sqrtf(bc2), gscale);
+    else
+        hipLaunchKernelGGL(adamw_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (uint16_t*)p16,
+                           n, lr, beta1, beta2, eps, weight_decay, 1.0f / bc1, 1.0f / sqrtf(bc2), (const float*)nullptr);
+    return wiw_check_launch(what);
+}
+
+extern "C" int wiw_adamw_step(void* stream, float* p, const float* g, float* m, float* v, void* p16, int64_t n, float lr,
+                              float beta1, float beta2, float eps, float weight_decay, int step) {
+    return adamw_launch(stream, p, g, m, v, p16, n, lr, beta1, beta2, eps, weight_decay, step, nullptr, "wiw_adamw_step");
+}
+
+extern "C" int wiw_adamw_step_scaled(void* stream, float* p, const float* g, float* m, float* v, void* p16, int64_t n, float lr,
+                                     float beta1, float beta2, float eps, float weight_decay, int step, const float* gscale) {
+    WIW_REQUIRE(gscale && (((uintptr_t)gscale) & 3) == 0, "adamw_scaled: gscale must be a device pointer to one fp32");
+    return adamw_launch(stream, p, g, m, v, p16, n, lr, beta1, beta2, eps, weight_decay, step, gscale, "wiw_adamw_step_scaled");
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Global gradient norm (gradient clipping as the reference's DeepSpeed ZeRO-1 config runs it): the sum of squares
+// of MANY fp32 tensors in one launch, then a one-block finalise.
+//   table[t] = (address, element count, index of the tensor's first chunk): tensor t is cut into chunks of WIW_SUMSQ_CHUNK
+//   elements (the last one shorter); chunk c of the whole table gets partial[c].  Which elements feed which partial, and in
+//   which order they are added, depends on the table alone — blocks walk the chunks grid-stride, so the grid size changes who
+//   computes a partial, never its value: bit-repeatable, no atomics.
+//   Inside a chunk the sum is PAIRWISE: 4 squares of a 16-byte load (2 levels), the 16 loads of a thread (4), the 64 lanes of
+//   a wave (6), the 4 waves (2) = log2(16384) levels, + 1 for the <= 3 head and <= 3 tail elements of a tensor whose address is
+//   not 16-byte aligned (they ride in lanes 0..2): relative error <= (log2(L) + 2) 2^-24 with the rounding of the squares.
+//   Inf / NaN propagate through the adds (nothing is compared or clamped): a non-finite element gives a non-finite total.
+// ---------------------------------------------------------------------------------------------------------------------
+constexpr int SUMSQ_CHUNK = 16384;     // elements: 256 threads x 16 loads x 4 floats (64 KB in flight per block)
+struct SumsqEntry {
+    const float* ptr;
+    int64_t n;
+    int64_t first_chunk;
+};
+typedef float sumsq_f32x4 __attribute__((ext_vector_type(4)));
+WIW_DEV float sq4(const sumsq_f32x4 a) { return (a.x * a.x + a.y * a.y) + (a.z * a.z + a.w * a.w); }
+
+__global__ __launch_bounds__(256) void grad_sumsq_kernel(const SumsqEntry* __restrict__ table, int n_tensors, int64_t n_chunks,
+                                                          float* __restrict__ partial) {
+    __shared__ float red[4];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    for (int64_t c = blockIdx.x; c < n_chunks; c += gridDim.x) {
+        int lo = 0, hi = n_tensors - 1;                       // the last tensor whose first chunk is <= c (block-uniform)
+        while (lo < hi) {
+            const int mid = (lo + hi + 1) >> 1;
+            if (table[mid].first_chunk <= c) lo = mid; else hi = mid - 1;
+        }
+        const SumsqEntry e = table[lo];
+        const int64_t off = (c - e.first_chunk) * SUMSQ_CHUNK;
+        // the addresses come out of a table in memory: tell the compiler they are global (global_load, not flat_load)
+        typedef const __attribute__((address_space(1))) float gfloat;
+        typedef const __attribute__((address_space(1))) sumsq_f32x4 gfloat4;
+        gfloat* __restrict__ base = (gfloat*)(e.ptr + off);
+        const int64_t left = e.n - off;
+        const int len = left < SUMSQ_CHUNK ? (int)left : SUMSQ_CHUNK;
+        int head = (int)((16 - ((uintptr_t)base & 15)) & 15) >> 2;      // scalar elements before the first 16-byte boundary
+        if (head > len) head = len;
+        const int nv = (len - head) >> 2, tail = len - head - 4 * nv;
+        gfloat4* __restrict__ body = (gfloat4*)(base + head);
+        float s[16];
+        if (nv == SUMSQ_CHUNK / 4) {
+#pragma unroll
+            for (int j = 0; j < 16; ++j) s[j] = sq4(body[j * 256 + tid]);
+        } else {
+#pragma unroll
+            for (int j = 0; j < 16; ++j) {
+                const int i = j * 256 + tid;
+                s[j] = i < nv ? sq4(body[i]) : 0.0f;
+            }
+        }
+#pragma unroll
+        for (int w = 1; w < 16; w <<= 1)
+#pragma unroll
+            for (int j = 0; j < 16; j += 2 * w) s[j] += s[j + w];
+        float extra = 0.0f;                                    // head and tail elements: lanes 0..2, disjoint addresses
+        if (tid < head) extra = base[tid] * base[tid];
+        if (tid < tail) {
+            const float t = base[head + 4 * nv + tid];
+            extra += t * t;
+        }
+        const float acc = wave_sum(s[0] + extra);
+        if (lane == 0) red[wave] = acc;
+        __syncthreads();
+        if (tid == 0) partial[c] = (red[0] + red[1]) + (red[2] + red[3]);
+        __syncthreads();
+    }
+}
+
+// One block: out[0] = sumsq = the partials added in INDEX order (thread t: partials t, t + 1024, ...; then a fixed tree), in
+// double; and, with max_norm > 0, out[1] = norm = sqrt(sumsq), out[2] = coef = min(1, max_norm / (norm + 1e-6)) in fp32 as
+// torch.nn.utils.clip_grad_norm_ computes it (a NaN norm gives a NaN coefficient: the comparison does not hide it),
+// out[3] = 1 if sumsq is finite else 0.  partial == NULL: out[0] is taken as given (the all-reduced sum of the ranks).
+__global__ __launch_bounds__(1024) void grad_norm_finalize_kernel(const float* __restrict__ partial, int64_t n_partial, float max_norm,
+                                                                   float* __restrict__ out) {
+    __shared__ double red[1024];
+    const int tid = threadIdx.x;
+    if (partial) {
+        double acc = 0.0;
+        for (int64_t i = tid; i < n_partial; i += 1024) acc += (double)partial[i];
+        red[tid] = acc;
+        __syncthreads();
+        for (int s = 512; s > 0; s >>= 1) {
+            if (tid < s) red[tid] += red[tid + s];
+            __syncthreads();
+        }
+    }
+    if (tid == 0) {
+        const float sumsq = partial ? (float)red[0] : out[0];
+        out[0] = sumsq;
+        if (max_norm > 0.0f) {
+            const float norm = (float)sqrt((double)sumsq);
+            float coef = max_norm / (norm + 1e-6f);
+            if (coef > 1.0f) coef = 1.0f;
+            out[1] = norm;
+            out[2] = coef;
+            out[3] = (sumsq - sumsq == 0.0f) ? 1.0f : 0.0f;      // false for Inf and NaN
+        }
+    }
+}
+
+extern "C" int wiw_grad_sumsq_chunk(void) { return SUMSQ_CHUNK; }
+
+extern "C" int wiw_grad_sumsq_partials(void* stream, const void* table, int n_tensors, int64_t n_chunks, float* partial, int blocks) {
+    WIW_REQUIRE(table && partial && n_tensors > 0 && n_chunks >= n_tensors, "grad_sumsq: null pointer or empty table");
+    WIW_REQUIRE((((uintptr_t)table) & 7) == 0 && (((uintptr_t)partial) & 3) == 0, "grad_sumsq: misaligned table / partials");
+    WIW_REQUIRE(blocks >= 0 && blocks <= 65536, "grad_sumsq: blocks in [0, 65536] (0: sized from the chunk count)");
+    int64_t grid = blocks > 0 ? blocks : 256 * 8;
+    if (grid > n_chunks) grid = n_chunks;
+    hipLaunchKernelGGL(grad_sumsq_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, (const SumsqEntry*)table, n_tensors,
+                       n_chunks, partial);
+    return wiw_check_launch("wiw_grad_sumsq_partials");
+}
+
+extern "C" int wiw_grad_norm_finalize(void* stream, const float* partial, int64_t n_partial, float max_norm, float* out) {
+    WIW_REQUIRE(out && (((uintptr_t)out) & 3) == 0, "grad_norm_finalize: out must point to 4 fp32");
+    WIW_REQUIRE(partial ? n_partial > 0 : max_norm > 0.0f, "grad_norm_finalize: partials with n_partial > 0, or a sum in out[0] and max_norm > 0");
+    WIW_REQUIRE(!(max_norm != max_norm) && max_norm < 3.0e38f, "grad_norm_finalize: max_norm must be finite (<= 0: the sum only)");
+    hipLaunchKernelGGL(grad_norm_finalize_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, partial, n_partial, max_norm, out);
+    return wiw_check_launch("wiw_grad_norm_finalize");
 }
 
 extern "C" int wiw_edm_loss_grad(void* stream, const float* pred, const float* noisy, const float* target, int64_t n,

@@ -172,6 +172,11 @@ EXPORTS = {
     "wiw_ema_step_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_float]),
     "wiw_adamw_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_float,
                                  C.c_float, C.c_float, C.c_float, C.c_float, C.c_int]),
+    "wiw_adamw_step_scaled": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_float,
+                                        C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, C.c_void_p]),
+    "wiw_grad_sumsq_chunk": (C.c_int, []),
+    "wiw_grad_sumsq_partials": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int]),
+    "wiw_grad_norm_finalize": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_void_p]),
     "wiw_edm_loss_grad": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_void_p,
                                     C.c_void_p, C.c_int]),
     "wiw_gather_taps_t_bf16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
@@ -261,6 +266,9 @@ class Hip:
         self._gn_cnt_pool = torch.zeros(40, 65536, dtype=torch.int32, device=self.device)
         self._gn_cnt = {}
         self._warmup_stream = None
+        self._sumsq_pin = None            # grad_sumsq: pinned staging copy of the table + the event of its last upload
+        self._sumsq_state = None          # grad_sumsq: (address / size key, device table, partials, chunk count) of the last call
+        self.sumsq_table_uploads = 0      # how often that table went to the device (tests / tools)
         # ... and this one for the non-GEMM kernels: (start_event, end_event, family, algorithmic_flops, algorithmic_bytes)
         self.kernel_profile = None
 
@@ -667,12 +675,80 @@ class Hip:
             "wiw_transpose_framepad_bf16"))
         return Y
 
-    def adamw_step(self, p, g, m, v, step, lr, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=1e-2, p16=None):
-        """torch.optim.AdamW on flat fp32 tensors, in place; `p16` (this Hip's 16-bit dtype) receives the refreshed copy."""
+    def adamw_step(self, p, g, m, v, step, lr, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=1e-2, p16=None, grad_scale=None):
+        """torch.optim.AdamW on flat fp32 tensors, in place; `p16` (this Hip's 16-bit dtype) receives the refreshed copy.
+        grad_scale: a one-element fp32 DEVICE tensor (the clipping coefficient, `grad_sumsq(...)[2:3]`); the kernel multiplies
+        every gradient element by it on load — `g` is not modified and the host never reads the value."""
         assert p.dtype == g.dtype == m.dtype == v.dtype == torch.float32 and p.numel() == g.numel() == m.numel() == v.numel()
         assert p16 is None or (p16.dtype == self.dtype and p16.numel() == p.numel())
-        self._ck(self.lib.wiw_adamw_step(self._stream(), _p(p), _p(g), _p(m), _p(v), _p(p16), p.numel(), lr, beta1, beta2,
-                                         eps, weight_decay, step), "wiw_adamw_step")
+        if grad_scale is None:
+            self._ck(self.lib.wiw_adamw_step(self._stream(), _p(p), _p(g), _p(m), _p(v), _p(p16), p.numel(), lr, beta1, beta2,
+                                             eps, weight_decay, step), "wiw_adamw_step")
+            return
+        assert grad_scale.dtype == torch.float32 and grad_scale.numel() == 1 and grad_scale.device == p.device
+        self._ck(self.lib.wiw_adamw_step_scaled(self._stream(), _p(p), _p(g), _p(m), _p(v), _p(p16), p.numel(), lr, beta1, beta2,
+                                                eps, weight_decay, step, _p(grad_scale)), "wiw_adamw_step_scaled")
+
+    # ---- global gradient norm / clipping (csrc/train.hip)
+    def grad_sumsq(self, tensors, max_norm: Optional[float] = None, blocks: int = 0) -> torch.Tensor:
+        """Sum of squares over a list of fp32 tensors (contiguous, any length >= 1, any 4-byte alignment) in ONE launch plus
+        a one-block finalise.  Returns a fresh fp32 device record [sumsq, norm, coef, finite]; with `max_norm` the last three
+        are filled by the same finalise launch (`coef = min(1, max_norm / (norm + 1e-6))`), without it only `sumsq` is
+        (all-reduce it, then `clip_coef`).  Nothing is read back to the host.
+        The (address, count) table lives on the device and is re-sent — as ONE copy — only when an address or a size
+        differs from the previous call's.  `blocks` (0: the library's choice) never changes the result, only who computes it."""
+        if isinstance(tensors, torch.Tensor):
+            tensors = [tensors]
+        key = []
+        for t in tensors:
+            assert t.dtype == torch.float32 and t.is_contiguous() and t.is_cuda and t.numel() > 0
+            key.append((t.data_ptr(), t.numel()))
+        assert key, "grad_sumsq: no tensors"
+        st = self._sumsq_state
+        if st is None or st[0] != key:
+            L = self.sumsq_chunk
+            rows, first = [], 0
+            for ptr, n in key:
+                rows.append((ptr, n, first))
+                first += (n + L - 1) // L
+            table = st[1] if st is not None and st[1].shape[0] >= len(rows) else torch.empty((max(len(rows), 2048), 3), dtype=torch.int64,
+                                                                                             device=self.device)
+            # ONE asynchronous host-to-device copy of the whole table, from pinned memory: a pageable copy would make the
+            # host wait for everything queued on the stream (the whole backward) and expose the per-parameter AdamW launches
+            # that follow; the event keeps the staging buffer from being rewritten under a copy still in flight
+            if self._sumsq_pin is None or self._sumsq_pin[0].shape[0] < table.shape[0]:
+                self._sumsq_pin = (torch.empty(table.shape, dtype=torch.int64).pin_memory(), torch.cuda.Event())
+            pin, done = self._sumsq_pin
+            done.synchronize()
+            pin[: len(rows)].copy_(torch.tensor(rows, dtype=torch.int64))
+            table[: len(rows)].copy_(pin[: len(rows)], non_blocking=True)
+            done.record()
+            partial = st[2] if st is not None and st[2].numel() >= first else torch.empty(first, dtype=torch.float32, device=self.device)
+            st = self._sumsq_state = (key, table, partial, first)
+            self.sumsq_table_uploads += 1
+        _, table, partial, n_chunks = st
+        rec = torch.zeros(4, dtype=torch.float32, device=self.device)
+        nbytes = 4.0 * sum(n for _, n in key)
+
+        def run():
+            self._ck(self.lib.wiw_grad_sumsq_partials(self._stream(), _p(table), len(key), n_chunks, _p(partial), int(blocks)),
+                     "wiw_grad_sumsq_partials")
+            self._ck(self.lib.wiw_grad_norm_finalize(self._stream(), _p(partial), n_chunks, 0.0 if max_norm is None else float(max_norm),
+                                                     _p(rec)), "wiw_grad_norm_finalize")
+        self._timed("grad_norm", 0.0, nbytes, run)
+        return rec
+
+    @property
+    def sumsq_chunk(self) -> int:
+        """Elements per partial of `grad_sumsq` (the L of its error bound (log2 L + 2) 2^-24)."""
+        return int(self.lib.wiw_grad_sumsq_chunk())
+
+    def clip_coef(self, rec: torch.Tensor, max_norm: float) -> torch.Tensor:
+        """Second half of `grad_sumsq` on its own: rec[0] holds a sum of squares (e.g. all-reduced over the ranks); fills
+        rec[1:4] = (norm, min(1, max_norm / (norm + 1e-6)), finite) in place, on the device."""
+        assert rec.dtype == torch.float32 and rec.numel() == 4 and rec.is_contiguous() and rec.is_cuda
+        self._ck(self.lib.wiw_grad_norm_finalize(self._stream(), None, 0, float(max_norm), _p(rec)), "wiw_grad_norm_finalize")
+        return rec
 
     def ema_step(self, shadow, param, one_minus_decay: float):
         """EMAModel.step on flat fp32 tensors, in place: shadow -= one_minus_decay * (shadow - param)."""

@@ -232,6 +232,32 @@ class ShardedWorker:
 # Fine-tuning (row f2): data-parallel gradient reduction with the optimiser state sharded over the ranks (ZeRO stage 1, what the
 # reference runs through accelerate + DeepSpeed: FTsvd/config/accelerate_deepspeed_o1_config.yaml, train_svd.py:954-968)
 # ------------------------------------------------------------------------------------------------
+def check_max_grad_norm(value) -> Optional[float]:
+    """None (clipping off) or a positive finite threshold; anything else is a configuration error."""
+    if value is None:
+        return None
+    if isinstance(value, bool) or not isinstance(value, (int, float)) or not (0.0 < float(value) < float("inf")):
+        raise ValueError(f"max_grad_norm must be None or a positive finite number, got {value!r}")
+    return float(value)
+
+
+class _TorchNormOps:
+    """CPU restatement of `Hip.grad_sumsq` / `Hip.clip_coef` for the gloo tests (same record, same fp32 coefficient formula)."""
+
+    @staticmethod
+    def grad_sumsq(tensors):
+        rec = torch.zeros(4, dtype=torch.float32, device=tensors[0].device)
+        rec[0] = sum(t.double().pow(2).sum() for t in tensors).float()
+        return rec
+
+    @staticmethod
+    def clip_coef(rec, max_norm):
+        rec[1] = rec[0].double().sqrt().float()
+        rec[2] = torch.clamp(torch.tensor(max_norm, dtype=torch.float32) / (rec[1] + 1e-6), max=1.0)
+        rec[3] = float(torch.isfinite(rec[0]))
+        return rec
+
+
 class ShardedAdamW:
     """fp32 master weights, AdamW moments and the update are SHARDED over the ranks; gradients are averaged with one
     reduce-scatter per bucket and the updated parameters return with one all-gather per bucket:
@@ -245,12 +271,28 @@ class ShardedAdamW:
     (default 256 MiB: few, large collectives) are what a backward pass hands over as soon as their gradients are complete —
     `reduce_bucket(i)` can be called from the backward's stream order; `step()` reduces whatever is still pending.
     gloo (CPU tests) has no reduce-scatter: there the bucket is all-reduced and sliced, which is arithmetically the same.
+
+    max_grad_norm (default None: off, nothing below runs): global-norm gradient clipping in DeepSpeed ZeRO-1's order, which is
+    what the reference's `gradient_clipping: 0.5` does — the sum of squares of THIS rank's averaged slices (`gshard`; its padding is
+    zero), one all-reduce(SUM) of that scalar, `coef = min(1, max_grad_norm / (norm + 1e-6))` (torch.nn.utils.clip_grad_norm_'s),
+    then `update_fn(..., grad_scale=coef)` with the coefficient as a one-element fp32 tensor on `device`: the update multiplies
+    the gradient by it on load (`Hip.adamw_step(grad_scale=)`), nothing is read back to the host, every rank takes the same value.
+    `norm_ops`: an object with `grad_sumsq(tensors)` and `clip_coef(record, max_norm)` — a `hip.Hip` on the GPU (required there: the
+    reduction is a HIP kernel); None on the CPU restates the two in torch (gloo tests).  `clip_record` keeps the last step's
+    [sumsq, norm, coef, finite] on the device.
     """
 
     def __init__(self, shapes, device, update_fn: Callable, bucket_elems: int = 64 * 1024 * 1024, lr: float = 1e-5,
-                 betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2):
+                 betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2, max_grad_norm: Optional[float] = None,
+                 norm_ops=None):
         self.rank, self.world = dist.get_rank(), dist.get_world_size()
         self.device, self.update_fn = device, update_fn
+        self.max_grad_norm = check_max_grad_norm(max_grad_norm)
+        if self.max_grad_norm is not None and norm_ops is None:
+            if torch.device(device).type != "cpu":
+                raise RuntimeError("ShardedAdamW(max_grad_norm=...) on a GPU needs norm_ops=<hip.Hip>: the norm is a HIP reduction")
+            norm_ops = _TorchNormOps()
+        self.norm_ops, self.clip_record = norm_ops, None
         self.lr, self.betas, self.eps, self.wd = lr, betas, eps, weight_decay
         self.offsets, off = {}, 0
         for name, shp in shapes.items():                      # flat layout in the given (model) order
@@ -347,7 +389,14 @@ class ShardedAdamW:
             if not self._reduced[b]:
                 self.reduce_bucket(b)
         self.steps += 1
-        self.update_fn(self.master, self.gshard, self.m, self.v, self.steps, self.lr, self.betas[0], self.betas[1], self.eps, self.wd)
+        if self.max_grad_norm is None:
+            self.update_fn(self.master, self.gshard, self.m, self.v, self.steps, self.lr, self.betas[0], self.betas[1], self.eps, self.wd)
+        else:
+            rec = self.norm_ops.grad_sumsq([self.gshard])                 # local partition first, then the ranks (ZeRO-1's order)
+            dist.all_reduce(rec[0:1], op=dist.ReduceOp.SUM)
+            self.clip_record = self.norm_ops.clip_coef(rec, self.max_grad_norm)
+            self.update_fn(self.master, self.gshard, self.m, self.v, self.steps, self.lr, self.betas[0], self.betas[1], self.eps, self.wd,
+                           grad_scale=rec[2:3])
         for b in range(self.n_buckets):
             dist.all_gather_into_tensor(self.params[b * self.bucket:(b + 1) * self.bucket],
                                         self.master[b * self.slice:(b + 1) * self.slice])

@@ -680,8 +680,27 @@ class Trainer:
 
     def __init__(self, net: "UNetTrain", lr: float = 1e-5, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2,
                  optimizer=None, loss_scale: Optional[float] = None, train_param_type: str = "full", grad_accum: int = 1,
-                 autotune: bool = False, scale_growth_interval: int = 2000, use_ema: bool = False, ema_kwargs: Optional[dict] = None):
+                 autotune: bool = False, scale_growth_interval: int = 2000, use_ema: bool = False, ema_kwargs: Optional[dict] = None,
+                 max_grad_norm: Optional[float] = None):
+        from .parallel import check_max_grad_norm
+
         self.net, self.lr, self.betas, self.eps, self.wd = net, lr, betas, eps, weight_decay
+        # global-norm gradient clipping, off by default.  The reference clips: DeepSpeed's ZeRO optimiser applies the
+        # `gradient_clipping: 0.5` of FTsvd/config/accelerate_deepspeed_o1_config.yaml (train_svd.py's own --max_grad_norm call,
+        # :965-967, is commented out).  The norm is taken over the window's MEAN gradient of the TRAINABLE parameters, after the
+        # loss-scale division and the accumulation, right before the update; the update kernels multiply by the coefficient.
+        # A sharded optimiser clips by its OWN setting (it sees the rank-averaged gradient); this argument is never handed to it.
+        self.max_grad_norm = check_max_grad_norm(max_grad_norm)
+        if optimizer is not None:
+            theirs = getattr(optimizer, "max_grad_norm", None)
+            if self.max_grad_norm is not None and theirs is not None and theirs != self.max_grad_norm:
+                raise ValueError(f"Trainer(max_grad_norm={self.max_grad_norm}) and its optimizer (max_grad_norm={theirs}) disagree")
+            if self.max_grad_norm is not None and theirs is None:
+                raise ValueError("Trainer(max_grad_norm=...) with an external optimizer: the optimizer clips — build it with the same "
+                                 "max_grad_norm (the Trainer does not configure it)")
+            self.max_grad_norm = theirs
+        # device record [sumsq, norm, coef, finite] of the last optimiser step, and what has been read from it
+        self._clip_rec, self._grad_norm, self._clip_coef = None, None, None
         # `--gradient_accumulation_steps` (train_svd.sh:20 runs 4; accelerate averages the micro-batch losses, train_svd.py:
         # 864, 961-969): `step` is one micro-batch, the optimiser runs on every grad_accum-th call with the mean gradient
         self.grad_accum, self._micro, self._acc = int(grad_accum), 0, {}
@@ -798,7 +817,10 @@ class Trainer:
             loss = self.step(st)
             if self.steps == before:          # accumulating micro-batch, or a skipped (overflowed) window: no optimiser step
                 continue
-            emit({"step": self.steps, "train_loss": loss, "lr": self.lr})
+            rec = {"step": self.steps, "train_loss": loss, "lr": self.lr}
+            if self.max_grad_norm is not None:                             # only with clipping on: today's records keep their keys
+                rec["grad_norm"] = self.grad_norm
+            emit(rec)
             if checkpointing_steps and output_dir and self.steps % checkpointing_steps == 0:
                 self.save(output_dir, checkpoints_total_limit)
             if validation_steps and val_samples and (self.steps % validation_steps == 0 or self.steps == 1):
@@ -856,6 +878,23 @@ class Trainer:
         torch.cuda.empty_cache()
         return out
 
+    @property
+    def grad_norm(self) -> Optional[float]:
+        """Global L2 norm of the gradient the last optimiser step saw, BEFORE clipping (None while clipping is off or before
+        the first step; non-finite for a window skipped on overflow).  Read lazily: `step` itself does not wait for it."""
+        return self._clip_values()[0]
+
+    @property
+    def clip_coef(self) -> Optional[float]:
+        """The factor the last optimiser step multiplied its gradient by: min(1, max_grad_norm / (grad_norm + 1e-6))."""
+        return self._clip_values()[1]
+
+    def _clip_values(self):
+        if self._clip_rec is not None:                 # one small device-to-host read, on demand
+            rec, self._clip_rec = self._clip_rec.tolist(), None
+            self._grad_norm, self._clip_coef = rec[1], rec[2]
+        return self._grad_norm, self._clip_coef
+
     def _mean_grad(self, name: str, g: torch.Tensor) -> torch.Tensor:
         """This micro-batch's share of the mean gradient plus what the earlier micro-batches of the window left."""
         if self.grad_accum == 1:
@@ -889,7 +928,26 @@ class Trainer:
         grads = net.backward(dpred.reshape(pred.shape), self.loss_scale)
         net.tape.after_op = None
         self._seen = {n for n in grads if self.trainable(n)}
-        if self.scaling:
+        clip_here = self.max_grad_norm is not None and self.opt is None and (self._micro + 1) % self.grad_accum == 0
+        flat = None
+        if clip_here:
+            # the window's mean gradient exists now: its norm record (one launch over all tensors + a one-block finalise) also
+            # carries the `finite` flag, which below replaces the per-tensor isfinite stack — the same single host read
+            if not overlapped and self.grad_accum > 1:
+                grads = {name: self._mean_grad(name, g) for name, g in grads.items() if self.trainable(name)}
+            flat = {name: g.reshape(-1).contiguous() for name, g in grads.items() if self.trainable(name)}
+            rec_dev = self._clip_rec = hip.grad_sumsq(list(flat.values()), self.max_grad_norm)
+        if self.scaling and clip_here:
+            rec = self._clip_rec.tolist()                                  # (one host sync)
+            self._clip_rec, self._grad_norm, self._clip_coef = None, rec[1], rec[2]
+            if rec[3] == 0.0:                                              # overflow: the same skip as below
+                self.loss_scale *= 0.5
+                self._good_steps = 0
+                self._micro, self._acc = 0, {}
+                if self.ema is not None:
+                    self.ema.step(net.master)
+                return float(loss)
+        elif self.scaling:
             bad = ~torch.stack([torch.isfinite(g).all() for g in grads.values()]).all()
             if self.opt is not None and self.opt.world > 1:                # EVERY rank skips, or none: the collectives of
                 import torch.distributed as dist                           # `opt.step()` must be entered by all of them
@@ -906,6 +964,8 @@ class Trainer:
                 self._micro, self._acc = 0, {}
                 if self.ema is not None:                                   # the window is over (`accelerator.sync_gradients`): the
                     self.ema.step(net.master)                              # reference steps the EMA on a skipped update too (:979)
+                if self.max_grad_norm is not None:                         # a non-finite gradient has no finite norm
+                    self._clip_rec, self._grad_norm, self._clip_coef = None, float("nan"), float("nan")
                 return float(loss)
         self._micro += 1
         if self._micro % self.grad_accum != 0:                             # not the last micro-batch: accumulate, no update
@@ -916,7 +976,7 @@ class Trainer:
                     self._acc[name] = g if name not in self._acc else self._acc[name] + g
             net.grads = {}
             return float(loss)
-        if not overlapped and self.grad_accum > 1:
+        if not overlapped and self.grad_accum > 1 and not clip_here:
             grads = {name: self._mean_grad(name, g) for name, g in grads.items() if self.trainable(name)}
         self._acc = {}
         self.steps += 1
@@ -926,12 +986,18 @@ class Trainer:
                 self.loss_scale, self._good_steps = min(self.loss_scale * 2.0, 2.0 ** 16), 0
         if self.opt is None:
             stale = set()
+            coef = None if flat is None else rec_dev[2:3]
             for name, g in grads.items():                                  # parameters without a gradient (the dead ones) stay
                 if not self.trainable(name):
                     continue
                 p, p16 = net.master[name], net._direct.get(name)            # plain-cast operands are refreshed by the kernel itself
-                hip.adamw_step(p.view(-1), g.reshape(-1).contiguous(), self.m[name].view(-1), self.v[name].view(-1), self.steps,
-                               self.lr, self.betas[0], self.betas[1], self.eps, self.wd, p16=None if p16 is None else p16.view(-1))
+                if flat is None:
+                    hip.adamw_step(p.view(-1), g.reshape(-1).contiguous(), self.m[name].view(-1), self.v[name].view(-1), self.steps,
+                                   self.lr, self.betas[0], self.betas[1], self.eps, self.wd, p16=None if p16 is None else p16.view(-1))
+                else:                                                      # every launch reads the same device scalar
+                    hip.adamw_step(p.view(-1), flat[name], self.m[name].view(-1), self.v[name].view(-1), self.steps,
+                                   self.lr, self.betas[0], self.betas[1], self.eps, self.wd, p16=None if p16 is None else p16.view(-1),
+                                   grad_scale=coef)
                 if p16 is None:
                     stale.add(name)
             net.refresh(stale)                                             # the re-laid-out operands (convolutions, padded inputs)
@@ -945,6 +1011,8 @@ class Trainer:
                         self.opt.view(self.opt.grads, name).copy_(g.reshape(net.master[name].shape))
             self.opt.lr = self.lr                                       # the caller's schedule (`train.lr_at`) sets Trainer.lr
             self.opt.step()
+            if self.max_grad_norm is not None:
+                self._clip_rec = self.opt.clip_record
             for name in grads:                                           # parameters without a gradient / frozen ones are not
                 if self.trainable(name):                                 # read back (torch.optim.AdamW skips them too)
                     net.master[name].copy_(self.opt.view(self.opt.params, name))

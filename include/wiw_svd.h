@@ -238,6 +238,22 @@ int wiw_temporal_attn_block_bf16(void* stream, const void* X, const void* Wqkv, 
                                  int batch, int T, int S, int heads, float eps, float scale, const void* zeros);
 
 /* ------------------------------------------------------------------------------------------------
+ * Prediction horizons of up to 32 frames (the 25-frame SVD-XT checkpoints; `--num_frames` of FTsvd/eval_inference.py:280):
+ * the 32-frame-slot siblings of the two entries above, which keep their limits (additive; the ABI version stays 17).
+ * One wave owns ONE spatial site of one head; S^T = K . Q^T is 32 x 32, the softmax runs over the <= 32 keys of a query,
+ * keys >= T are masked and their V rows zeroed (a padding slot never reaches O).  No allocation, no synchronisation, no
+ * atomics: graph-capture safe, bit-repeatable, batch items independent.
+ * wiw_attn_temporal32_bf16: the operands of wiw_attn_temporal_bf16, 1 <= T <= 32; QKV 16-byte and O 8-byte aligned,
+ *   ldqkv % 8 == 0, ldo % 4 == 0.
+ * wiw_temporal_attn_block32_bf16: the operands of wiw_temporal_attn_block_bf16 (the SAME gamma-folded tiled weights and fold
+ *   vectors; no `zeros` argument), 1 <= T <= 32; all pointers 16-byte aligned, ldo % 8 == 0, X and O below 4 GiB.
+ * ---------------------------------------------------------------------------------------------- */
+int wiw_attn_temporal32_bf16(void* stream, const void* QKV, int ldqkv, void* O, int ldo, int batch, int T, int S,
+                             int heads, float scale);
+int wiw_temporal_attn_block32_bf16(void* stream, const void* X, const void* Wqkv, const float* fold, void* O, int ldo,
+                                   int batch, int T, int S, int heads, float eps, float scale);
+
+/* ------------------------------------------------------------------------------------------------
  * FUSED FeedForward (GEGLU) of the 320-channel level, optionally with the LayerNorm in front of it, ONE kernel:
  *
  *   h   = GEGLU( LN?(X) . W1^T + b1 )            [M][1280], never written to memory

@@ -117,6 +117,10 @@ EXPORTS = {
                                          C.c_int, C.c_int, C.c_float]),
     "wiw_temporal_attn_block_bf16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                                                C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p]),
+    "wiw_attn_temporal32_bf16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                           C.c_int, C.c_int, C.c_float]),
+    "wiw_temporal_attn_block32_bf16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                                 C.c_int, C.c_int, C.c_int, C.c_float, C.c_float]),
     "wiw_ffn_geglu_bf16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_int, C.c_float, C.c_float,
                                      C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_float]),
@@ -407,6 +411,23 @@ class Hip:
             self.lib.wiw_temporal_attn_block_bf16(self._stream(), _p(X), _p(Wqkv), _p(fold), _p(O), ldo, batch, T, S,
                                                   heads, eps, scale, self.zeros.data_ptr()),
             "wiw_temporal_attn_block_bf16"))
+        return O
+
+    def attn_temporal32(self, QKV, ldqkv, O, ldo, batch, T, S, heads, scale):
+        """`attn_temporal` for up to 32 frames (temporal32.hip)."""
+        self._timed("attn_temporal", 4.0 * batch * S * heads * T * T * 64, 8.0 * batch * T * S * heads * 64, lambda: self._ck(
+            self.lib.wiw_attn_temporal32_bf16(self._stream(), _p(QKV), ldqkv, _p(O), ldo, batch, T, S, heads, scale),
+            "wiw_attn_temporal32_bf16"))
+        return O
+
+    def temporal_attn_block32(self, X, Wqkv, fold, O, ldo, batch, T, S, heads, eps, scale):
+        """`temporal_attn_block` for up to 32 frames (temporal32.hip): the same operands, the same accounting."""
+        Cn, M = heads * 64, batch * T * S
+        self._timed("temporal_block", 2.0 * M * 3 * Cn * Cn + 4.0 * batch * S * heads * T * T * 64,
+                    2.0 * (2 * M * Cn + 3 * Cn * Cn), lambda: self._ck(
+            self.lib.wiw_temporal_attn_block32_bf16(self._stream(), _p(X), _p(Wqkv), _p(fold), _p(O), ldo, batch, T, S,
+                                                    heads, eps, scale),
+            "wiw_temporal_attn_block32_bf16"))
         return O
 
     def ffn_geglu(self, X, W1, b1, W2, b2, out, M, *, ldx=FFN_C, rowvec=None, rowvec_ld=0, rows_per_vec=1, res1=None, ldr1=0,

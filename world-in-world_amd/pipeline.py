@@ -201,9 +201,10 @@ class SVDDenoiser:
     # ---- hipGraph cache (capture is default-on in the server; a pool of ~6 GB per candidate must not be taken blindly)
     def graph_pool_estimate(self, B: int, h: int, w: int) -> float:
         """Bytes a captured forward pins for (B candidates, h x w latent): ~6.2 GB per candidate at 72x128 with 16-bit
-        activations (measured, serve_worker --help), x 1.6 with the fp32 residual stream; linear in B h w."""
+        activations and 14 frames (measured, serve_worker --help), x 1.6 with the fp32 residual stream; linear in B h w and in
+        the frame count (every activation of the forward has T * h * w rows per candidate)."""
         per = 6.2e9 * (1.6 if getattr(self.unet, "res32_any", False) else 1.0)
-        return per * B * (h * w) / (72.0 * 128.0)
+        return per * B * (h * w) / (72.0 * 128.0) * self.unet.cfg.num_frames / 14.0
 
     def graph_status(self) -> dict:
         """For the server's status line / logs: what is captured, what was refused and why."""

@@ -1,4 +1,4 @@
-"""The SVD world-model worker: request dict -> 14-frame rollouts -> response dict.
+"""The SVD world-model worker: request dict -> `num_frames`-frame rollouts (14 by default, up to 32) -> response dict.
 
 Mirrors `do_some_tasks` / `Navigator.inference` of the reference worker
 (FTsvd/eval_inference.py:228-266, 313-349) with the same fixed knobs (fps 7, motion bucket 127,
@@ -31,6 +31,10 @@ import numpy as np
 
 from . import plumbing as P
 from .protocol import DONE, read_framed, read_pickled, write_framed, write_pickled
+
+
+MAX_NUM_FRAMES = 32   # frame slots of the temporal attention kernels (csrc/temporal32.hip); `validate_args` refuses more
+VAE_WIDEST_ROW_BYTES = 128 * 2   # the temporal decoder's last level: 128 channels, 16-bit, at the full output resolution
 
 
 class Frontend(Protocol):
@@ -379,6 +383,15 @@ def validate_args(args) -> None:
         if v is not None and (v <= 0 or v % 64 != 0):
             raise SystemExit(f"--{flag} {v}: the output size must be a positive multiple of 64 (the latent is 1/8 of it and "
                              f"the UNet halves it three times)")
+    if not 1 <= args.num_frames <= MAX_NUM_FRAMES:
+        raise SystemExit(f"--num_frames {args.num_frames}: this build serves 1 <= num_frames <= {MAX_NUM_FRAMES} (the temporal "
+                         f"attention kernels hold a site's frames in {MAX_NUM_FRAMES} slots, csrc/temporal32.hip)")
+    w_, h_ = getattr(args, "width", None), getattr(args, "height", None)
+    if w_ and h_ and args.num_frames * w_ * h_ * VAE_WIDEST_ROW_BYTES >= 1 << 32:
+        raise SystemExit(f"--num_frames {args.num_frames} at {w_}x{h_}: the clip is decoded whole (decode_chunk_size = num_frames, "
+                         f"pipeline:291-302; chunking changes the temporal convolutions) and the decoder's widest activation, "
+                         f"{args.num_frames} x {h_} x {w_} rows of {VAE_WIDEST_ROW_BYTES} bytes, would reach 4 GiB: no kernel on "
+                         f"that path has been run past 32-bit byte offsets (25 frames at 1024x576 is 3.8 GB and served)")
     if args.num_past_obs != 1:
         raise SystemExit(f"--num_past_obs {args.num_past_obs}: the WM-server protocol carries ONE conditioning image per candidate "
                          f"(the reference's served path asserts past_obs_pixel is None, eval_inference.py:236-242); P > 1 tokens are "

@@ -78,9 +78,16 @@ def _pad_rows(t: torch.Tensor, mult: int = 64) -> torch.Tensor:
     return out
 
 
+TRAIN_MAX_FRAMES = 16   # `self_attention` pads the temporal sequences to Tp = 16 rows
+
+
 class UNetTrain:
     def __init__(self, cfg: UNetConfig, state_dict: Dict[str, torch.Tensor], device="cuda:0", hip: Optional[Hip] = None,
                  dtype: torch.dtype = torch.bfloat16):
+        if cfg.num_frames > TRAIN_MAX_FRAMES:
+            raise ValueError(f"num_frames = {cfg.num_frames}: fine-tuning is built for at most {TRAIN_MAX_FRAMES} frames (the "
+                             f"temporal self-attention and its backward pad every site's sequence to {TRAIN_MAX_FRAMES} rows); "
+                             f"longer horizons are served by UNetHIP only")
         self.cfg = cfg
         self.device = torch.device(device)
         self.hip = hip or Hip(self.device, dtype)

@@ -160,7 +160,17 @@ def _require_single_key(ehs: torch.Tensor, max_tokens: int = 1) -> None:
                                   f"cross-attention needs UNetHIP(..., num_past_obs = P), P <= 8)")
 
 
+MAX_NUM_FRAMES = 32   # frame slots of the temporal attention kernels (csrc/temporal32.hip)
+
+
 class UNetHIP:
+    # 17 <= num_frames <= 32: levels of at most this many channels take the fused 32-slot temporal block
+    # (wiw_temporal_attn_block32_bf16), wider ones LayerNorm + QKV GEMM + wiw_attn_temporal32_bf16.  Decided per level by the
+    # same-process A/B of tools/horizon_probe.py (the fused kernel wins at C = 320, 635 vs 786 us, and loses
+    # at C = 640 / 1280, where the tuned 256x160 GEMM outruns its plain K loop); 0 / a large value force one path everywhere
+    # (tests, probe).  The unfused chain is also the fall-back past the fused kernel's 4-GiB limit.
+    FUSED32_MAX_C = 320
+
     def __init__(self, cfg: UNetConfig, state_dict: Dict[str, "torch.Tensor | np.ndarray"], device="cuda:0",
                  hip: Optional[Hip] = None, dtype: torch.dtype = torch.bfloat16, fold_layernorm: bool = False,
                  residual_fp32: "Optional[bool | str]" = None, num_past_obs: int = 1):
@@ -187,6 +197,8 @@ class UNetHIP:
         default: measured -0.7 % on the rollout (the in-kernel row statistics cost the K = 320 GEMMs more than the four
         LayerNorm passes per block they replace)."""
         self.cfg = cfg
+        if not 1 <= cfg.num_frames <= MAX_NUM_FRAMES:
+            raise ValueError(f"num_frames = {cfg.num_frames}: the temporal attention kernels hold 1 .. {MAX_NUM_FRAMES} frames")
         if not 1 <= int(num_past_obs) <= 8:
             raise ValueError(f"num_past_obs = {num_past_obs}: 1 .. 8 conditioning tokens per candidate")
         self.max_ctx = int(num_past_obs)
@@ -668,8 +680,10 @@ class UNetHIP:
             a = hip.layernorm(hs, M, Cn, w[t + ".norm_in.weight"], w[t + ".norm_in.bias"], addvec=cond.pos_emb[p],
                               addvec_ld=Cn, rows_per_vec=S, sum_out=hm, out=a)
         # ---- temporal block (attention.py:707-762); rows stay in (b,t,s) order
-        t_fused = T <= 14 and M * Cn * 2 < (1 << 32)      # else the unfused form below: the fused kernel's shape limits
-        w16 = f32 and t_fused                 # ff_in's output is fp32 and the fused temporal block wants its 16-bit rounding
+        # T <= 14: the 16-slot fused kernel; 15..16: unfused, 16-slot attention; 17..32: the 32-slot kernels of temporal32.hip
+        # (fused at C <= FUSED32_MAX_C unless the tensor is past the fused kernels' 4-GiB 32-bit offsets: then the unfused chain)
+        t_fused = (T <= 14 or (T > 16 and Cn <= self.FUSED32_MAX_C)) and M * Cn * 2 < (1 << 32)
+        w16 = f32 and t_fused                # ff_in's output is fp32 and the fused temporal block wants its 16-bit rounding
         hm = self._geglu_ff(a, t + ".ff_in", M, Cn, ln_input=hm if (fold_ff and fold_emb) else None, res1=hm, ldr1=Cn, beta1=1.0,
                             f32=f32, want16=w16)
         if t_fused:
@@ -677,13 +691,13 @@ class UNetHIP:
             # Q/K/V never leave the registers — no LayerNorm pass, no 3C-wide QKV tensor.  (fp32 stream: the kernel reads the
             # stream tensor's 16-bit rounding, written beside it by its producer.)
             hm, hm16 = hm if w16 else (hm, hm)
-            hip.temporal_attn_block(hm16, w[t + ".attn1.fused.weight"], w[t + ".attn1.fused.fold"], o, Cn, batch, T, S,
-                                    heads, 1e-5, scale)
+            block = hip.temporal_attn_block if T <= 14 else hip.temporal_attn_block32
+            block(hm16, w[t + ".attn1.fused.weight"], w[t + ".attn1.fused.fold"], o, Cn, batch, T, S, heads, 1e-5, scale)
         else:
             a = hip.layernorm(hm, M, Cn, w[t + ".norm1.weight"], w[t + ".norm1.bias"], out=a)
             qkv = self._empty(M, 3 * Cn)
             hip.gemm(a, w[t + ".attn1.to_qkv.weight"], qkv, M=M, N=3 * Cn, K=Cn, C1=Cn)
-            hip.attn_temporal(qkv, 3 * Cn, o, Cn, batch, T, S, heads, scale)
+            (hip.attn_temporal if T <= 16 else hip.attn_temporal32)(qkv, 3 * Cn, o, Cn, batch, T, S, heads, scale)
         if cond.P > 1:
             hm = self._linear(o, t + ".attn1.to_out.0", M, res1=hm, out_f32=f32)
             hm = self._cross_attention(t, hm, M, Cn, T * S, heads, cond)

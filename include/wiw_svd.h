@@ -109,6 +109,11 @@ int wiw_device_check(int dev, char* name, int name_len);
  *   with WIW_EPI_GEGLU, s and t follow the packed row order of W.  Served by the 256x160 / 128x160 tiles.
  * Constraints: C1, C2, C3 % 64 == 0; K = C1 + C2 (dense), taps * C1 (conv) or 9 * C1 + C2 + C3 (conv3x3 + shortcut);
  * A2 only with WIW_A_DENSE / WIW_A_CONV3X3, A3 only with WIW_A_CONV3X3.
+ * Alignment of the fp32 vectors: `bias` and `rowvec` need 4 bytes.  With both 16-byte aligned and rowvec_ld % 4 == 0 a launch
+ *   takes the vectorised epilogues (staged 16-bit rows, the fragment-layout fp32-stream epilogue, the 256x320 tile); otherwise
+ *   it runs the element-wise epilogue of the 256x160 / 128x160 tiles — same result contract, slower.  16 bytes are REQUIRED
+ *   (WIW_EINVAL otherwise) for `bias` with WIW_EPI_GEGLU, for `rowvec` (and rowvec_ld % 4 == 0) with WIW_EPI_LNFOLD, for
+ *   `bias` / `rowvec` / `res1` / `res2` / `out` with split-K, and always for `lnfold`.
  * ---------------------------------------------------------------------------------------------- */
 enum { WIW_A_DENSE = 0, WIW_A_CONV3X3 = 1, WIW_A_CONV3X3_S2 = 2, WIW_A_CONV3X3_UP = 3, WIW_A_CONV_T3 = 4,
        WIW_A_CONV3X3_S2P = 5 };
@@ -385,6 +390,8 @@ int wiw_cross_attn_fewkeys_bf16(void* stream, const void* Q, int ldq, const void
  * Replaces nn.LayerNorm at dp/models/attention.py:371,401,432,659-694, the `hidden_states + emb`
  * of transformer_temporal.py:352-353 and the residual add of the single-key cross-attentions
  * (attention.py:545-551, 740-743; exact elision).   C % 8 == 0, C <= 2048.
+ * Rows are dense ([rows][C]) and read / written in 16-byte pieces: X, gamma, beta, addvec (with addvec_ld % 4 == 0), sum_out and
+ * out must be 16-byte aligned (not checked), for wiw_layernorm_f32in likewise; wiw_cast_f32_to_16: X and out 16-byte aligned.
  * ---------------------------------------------------------------------------------------------- */
 int wiw_layernorm_bf16(void* stream, const void* X, int64_t rows, int C, const float* gamma, const float* beta,
                        float eps, const float* addvec, int addvec_ld, int rows_per_vec, void* sum_out, void* out);
@@ -408,6 +415,7 @@ int wiw_calib_mfma_random(void* stream, int blocks, int iters, const void* src, 
  * resnet.py:343-344 applied once:  out[(i*T + t)][c] = silu(time[i][c] + act[(i % B)*T + t][c] + noise[i][c])
  * (contract of SURVEY.md §9.2: candidate i % B's actions — NOT the reference's cross-wiring).
  *   time, noise: fp32 [Bc][E];  act: fp32 [B*T][E];  out: bf16 [Bc*T][E]
+ *   element-wise accesses: the natural alignment of the element types (4 bytes fp32, 2 bytes out), any E.
  * ---------------------------------------------------------------------------------------------- */
 int wiw_emb_combine(void* stream, const float* time, const float* act, const float* noise, int Bc, int B, int T,
                     int E, void* out);
@@ -418,6 +426,7 @@ int wiw_emb_combine(void* stream, const float* time, const float* act, const flo
  *   X[...][4:8]                = (i < B) ? 0 : image_latents[i - B][:, p]        (CFG halves)
  *   X[...][8:Cpad]             = 0   (channel padding so conv_in runs on the MFMA conv kernel)
  *   latents fp32 (B,T,4,h,w); image_latents fp32 (B,4,h,w); X bf16 [2B*T*h*w][Cpad]
+ *   latents / image_latents 4-byte aligned; X 16-byte aligned (whole 16-byte channel chunks are stored, padding included).
  * ---------------------------------------------------------------------------------------------- */
 int wiw_prep_unet_input(void* stream, const float* latents, const float* image_latents, int B, int T, int hw,
                         float sigma, int Cpad, void* X);
@@ -427,6 +436,7 @@ int wiw_prep_unet_input(void* stream, const float* latents, const float* image_l
  *   v  = v_u + g_t (v_c - v_u),  g_t = gmin + (gmax - gmin) * t / (T - 1)
  *   x0 = -sigma/sqrt(sigma^2+1) v + x/(sigma^2+1);   x += (x - x0)/sigma * (sigma_next - sigma)
  *   V fp32 [2B*T*h*w][ldv] (UNet output, channels 0..3); latents fp32 (B,T,4,h,w) updated in place.
+ *   V and latents 4-byte aligned, any ldv >= 4 (scalar accesses; columns 4 .. ldv-1 of V are not read).
  * ---------------------------------------------------------------------------------------------- */
 int wiw_cfg_euler_step(void* stream, const float* V, int ldv, float* latents, int B, int T, int hw, float sigma,
                        float sigma_next, float gmin, float gmax);
@@ -440,7 +450,7 @@ int wiw_cfg_euler_step(void* stream, const float* V, int ldv, float* latents, in
  *   single-head, head_dim = C attention of the VAE mid blocks (legacy AttnProcessor of
  *   dp/models/attention_processor.py as instantiated by dp/models/unets/unet_2d_blocks.py UNetMidBlock2D and
  *   unet_3d_blocks.py:930-990 MidBlockTemporalDecoder): scores = scale * Q.K^T and P.V are wiw_gemm_bf16 calls.
- *   cols % 4 == 0, cols <= 16384, ldx / ldp % 4 == 0.
+ *   cols % 4 == 0, cols <= 16384, ldx / ldp % 4 == 0; X 16-byte and P 8-byte aligned (not checked).
  * wiw_vae_time_conv_out: the decoder's last layer, Conv3d(3, 3, (3,1,1), padding (1,0,0))
  *   (dp/models/autoencoders/autoencoder_kl_temporal_decoder.py:87-161 `time_conv_out`) fused with the
  *   NHWC -> NCHW frame layout:  Y fp32 [frames*HW][ldy] (channels 0..2, ldy % 4 == 0), weight fp32 [3][3][3]

@@ -47,7 +47,9 @@ def test_attn_small(hip, seqs, S, heads, D):
     Sp = -(-S // 16) * 16
     q, k, v = (bf(rnd(seqs, Sp, C, seed=s, scale=1.2)) for s in (1, 2, 3))
     qk = torch.cat([q, k], -1).reshape(seqs * Sp, 2 * C).to(DEV, torch.bfloat16).contiguous()
-    vt = v.reshape(seqs * Sp, C).t().to(DEV, torch.bfloat16).contiguous()
+    vpad = v.clone()
+    vpad[:, S:] = float("nan")          # V^T columns S .. Sp-1 are padding: a masked key must be selected away, not multiplied by 0
+    vt = vpad.reshape(seqs * Sp, C).t().to(DEV, torch.bfloat16).contiguous()
     o = torch.full((seqs * Sp, C), float("nan"), dtype=torch.bfloat16, device=DEV)
     hip.attn_small(qk, 2 * C, C, vt, seqs * Sp, o, C, seqs, S, Sp, heads, D, D ** -0.5)
 

@@ -161,7 +161,16 @@ __global__ __launch_bounds__(256) void attn_small_kernel(const uint16_t* __restr
 #pragma unroll
         for (int db = 0; db < NDB; ++db) {
             // V^T fragment: lane = d row (db*16 + fr), 4 consecutive keys 16*kt + 4*fq .. +3 (8-byte aligned: Sp % 16 == 0)
-            const uint2 vv = *(const uint2*)(Vt + (int64_t)(h * D + db * 16 + fr) * ldvt + row0 + kt * 16 + fq * 4);
+            uint2 vv = *(const uint2*)(Vt + (int64_t)(h * D + db * 16 + fr) * ldvt + row0 + kt * 16 + fq * 4);
+            // keys >= S (last tile only): their V^T columns are padding that may hold anything — SELECTED away, a zero
+            // probability times an Inf / NaN would reach O
+            const int k0 = kt * 16 + fq * 4;
+            if (k0 + 3 >= S) {
+                if (k0 >= S) vv.x &= 0xffff0000u;
+                if (k0 + 1 >= S) vv.x &= 0x0000ffffu;
+                if (k0 + 2 >= S) vv.y &= 0xffff0000u;
+                if (k0 + 3 >= S) vv.y &= 0x0000ffffu;
+            }
             union { uint32_t u[4]; bf16x8 v; } vo;
             vo.u[0] = vv.x; vo.u[1] = vv.y; vo.u[2] = 0u; vo.u[3] = 0u;
             f32x4 acc = o[db];

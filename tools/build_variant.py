@@ -1,9 +1,8 @@
 #!/usr/bin/env python
-"""Build an A/B variant of the C-ABI library: the bf16 sources with extra -D flags on chosen files, linked to
+"""Build a variant of the C-ABI library (the trace builds, or an A/B experiment): the bf16 sources with extra -D flags on chosen files, linked to
 tools/ablate/libwiw_<name>.so (git-ignored; travels to the GPU box).  Load it with WIW_LIB=tools/ablate/libwiw_<name>.so.
 
     python tools/build_variant.py trace ffn.hip:-DWIW_FFN_TRACE
-    python tools/build_variant.py noge  ffn.hip:-DFFN_ABLATE=1
 Files without a flag spec reuse the objects of the regular build (world-in-world_amd/build/)."""
 import os
 import subprocess

@@ -15,21 +15,11 @@
 #include <type_traits>
 
 #include "common.h"
+#include "lds_dma.h"
 
 namespace {
 
-typedef const __attribute__((address_space(1))) void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
-WIW_DEV void glds16(const char* g, char* l) { __builtin_amdgcn_global_load_lds((gptr_t)g, (lptr_t)l, 16, 0, 0); }
-
 constexpr float LOG2E = 1.4426950408889634f;
-#ifndef WIW_ATTN_MIN_WAVES
-#define WIW_ATTN_MIN_WAVES 2   // launch-bounds hint (waves per SIMD); the kernel needs 126 VGPRs = 4 waves per SIMD on its own
-#endif                         // (5: capped at 96 VGPRs, 27 spilled in the tile loop: 7.2 instead of 3.5 ms at S = 9216)
-#ifndef WIW_ATTN_ABLATE
-#define WIW_ATTN_ABLATE 0   // timing experiments only (results wrong): 1 no max / exp2 (P = bf16(S)), 2 no K/V DMA + no tile
-#endif                      // barrier (stale stage 0), 4 no P.V MFMAs, 8 no Q.K MFMAs
-
 // v_max_f32 / v_max3_f32 without the canonicalising self-max hipcc puts in front of fmaxf (IEEE NaN quieting): the file is built
 // with -fno-honor-nans, under which the BUILTIN gives the bare instruction (the softmax loop is VALU-issue bound, every
 // instruction of it counts; a NaN score still ends in a NaN row, its exp2 is NaN whatever the reference maximum is).
@@ -70,7 +60,9 @@ WIW_DEV int64_t tail_sv(float*) { return 0; }
 WIW_DEV int64_t tail_sv(int64_t sv) { return sv; }
 
 template <int NWV, bool WLSE, bool PADV>
-__global__ __launch_bounds__(NWV * 64, WIW_ATTN_MIN_WAVES) void attn_spatial_kernel(const uint16_t* __restrict__ QK, int ldqk, int k_col_off,
+// launch-bounds hint of 2 waves per SIMD; the kernel needs 126 VGPRs = 4 waves per SIMD on its own (a hint of 5 caps it at
+// 96 VGPRs, 27 spilled in the tile loop: 7.2 instead of 3.5 ms at S = 9216)
+__global__ __launch_bounds__(NWV * 64, 2) void attn_spatial_kernel(const uint16_t* __restrict__ QK, int ldqk, int k_col_off,
                                                                const uint16_t* __restrict__ Vt, int64_t ldvt,
                                                                uint16_t* __restrict__ O, int ldo, int S, int heads,
                                                                int q_tiles, float scale_log2e, const char* zeros,
@@ -147,9 +139,7 @@ __global__ __launch_bounds__(NWV * 64, WIW_ATTN_MIN_WAVES) void attn_spatial_ker
                 glds16(key0 < S ? vp_(i) : zeros, sV + i * 1024);
             }
         }
-#ifndef WIW_ATTN_STATIC_KV   // ablation build: every tile re-reads KV tile 0 (cache-hot operands)
         kp0 += kstep; vp0 += KB * 2;
-#endif
     };
 
     f32x4 o[4][2];
@@ -171,12 +161,8 @@ __global__ __launch_bounds__(NWV * 64, WIW_ATTN_MIN_WAVES) void attn_spatial_ker
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     for (int kt = 0; kt < nkt; ++kt) {
-#if WIW_ATTN_ABLATE & 2
-        const char* sK = smem;
-#else
         if (kt + 1 < nkt) issue((kt + 1) & 1, kt + 1);
         const char* sK = smem + (kt & 1) * KV_STAGE;
-#endif
         const char* sV = sK + 8192;
         // ---- S^T = K . Q^T  (4 key frags x 2 query frags x 2 d steps)
         f32x4 s[4][2];
@@ -194,14 +180,9 @@ __global__ __launch_bounds__(NWV * 64, WIW_ATTN_MIN_WAVES) void attn_spatial_ker
             const bf16x8 k1 = *(const bf16x8*)(rowp + (((4 + fq) ^ (krow & 7)) << 4));
 #pragma unroll
             for (int f = 0; f < 2; ++f) {
-#if WIW_ATTN_ABLATE & 8
-                s[kf][f] = f32x4{0.f, 1.f, 2.f, 3.f};
-                asm volatile("" : "+v"(s[kf][f]) : "v"(k0), "v"(k1));
-#else
                 f32x4 z = f32x4{0.f, 0.f, 0.f, 0.f};
                 z = WIW_MFMA(k0, qf[f][0], z);
                 s[kf][f] = WIW_MFMA(k1, qf[f][1], z);
-#endif
             }
         }
         // ---- online softmax over keys (rows of S^T); lane owns query column fr of each query frag.
@@ -217,15 +198,6 @@ __global__ __launch_bounds__(NWV * 64, WIW_ATTN_MIN_WAVES) void attn_spatial_ker
                         if (kt * KB + (kf >> 1) * 32 + fq * 8 + (kf & 1) * 4 + r >= S) s[kf][f][r] = -INFINITY;
         }
         uint32_t pb[2][4][2];   // [query frag][key frag][2 dwords] = packed bf16x4 B operands of the K = 16 MFMAs
-#if WIW_ATTN_ABLATE & 1
-#pragma unroll
-        for (int f = 0; f < 2; ++f)
-#pragma unroll
-            for (int kf = 0; kf < 4; ++kf) {
-                pb[f][kf][0] = pack2bf(s[kf][f][0], s[kf][f][1]);
-                pb[f][kf][1] = pack2bf(s[kf][f][2], s[kf][f][3]);
-            }
-#else
 #pragma unroll
         for (int f = 0; f < 2; ++f) {
             float ma = max3_raw(s[0][f][0], s[0][f][1], s[0][f][2]);   // two interleaved chains (dependent VALU: 8.5 cycles each)
@@ -266,7 +238,6 @@ __global__ __launch_bounds__(NWV * 64, WIW_ATTN_MIN_WAVES) void attn_spatial_ker
                 pb[f][kf][1] = pack2bf(p2, p3);
             }
         }
-#endif
         // ---- O^T += V^T . P^T  (4 d frags x 2 query frags x 2 key steps); both operands in the natural K enumeration
         // thanks to the key permutation of the S^T fragments above
 #pragma unroll
@@ -283,19 +254,13 @@ __global__ __launch_bounds__(NWV * 64, WIW_ATTN_MIN_WAVES) void attn_spatial_ker
                     union { uint32_t u[4]; bf16x8 v; } pv;
                     pv.u[0] = pb[f][2 * ks][0]; pv.u[1] = pb[f][2 * ks][1];
                     pv.u[2] = pb[f][2 * ks + 1][0]; pv.u[3] = pb[f][2 * ks + 1][1];
-#if WIW_ATTN_ABLATE & 4
-                    asm volatile("" : "+v"(o[d][f]) : "v"(va.v), "v"(pv.v));
-#else
                     o[d][f] = WIW_MFMA(va.v, pv.v, o[d][f]);
                     if (d == 0) l_acc[f] = WIW_MFMA(ones, pv.v, l_acc[f]);
-#endif
                 }
             }
         }
-#if !(WIW_ATTN_ABLATE & 2)
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
-#endif
     }
     // ---- normalise and store: lane holds O[query fr][d = dfrag*16 + 4*fq + r]
 #pragma unroll

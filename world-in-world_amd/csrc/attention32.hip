@@ -48,23 +48,17 @@
 // the tolerance — and differed by an ulp from launch to launch (profiles/r12c_attn32_nonrepeatable_hunt.txt: it looked like
 // an LDS ring race for a while; 2 instead of 3 blocks per CU hid it).  Everything that touches an accumulator is a builtin now.
 #include "common.h"
+#include "lds_dma.h"
 
 namespace {
 
-typedef const __attribute__((address_space(1))) void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-WIW_DEV void glds16(const char* g, char* l) { __builtin_amdgcn_global_load_lds((gptr_t)g, (lptr_t)l, 16, 0, 0); }
 
 #ifdef WIW_F16
 #define WIW_MFMA32(a, b, c) \
     __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(wiw_h16x8, a), __builtin_bit_cast(wiw_h16x8, b), c, 0, 0, 0)
 #else
 #define WIW_MFMA32(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0)
-#endif
-
-#ifndef WIW_A32_WAVES
-#define WIW_A32_WAVES 3   // waves per SIMD the register budget is cut for (3: 168 VGPRs, no spill; 2: 256 — measured 2 % slower)
 #endif
 
 // v_max3_f32 / v_max_f32 through the BUILTIN (the file is built with -fno-honor-nans, so no canonicalising self-max is added).
@@ -94,7 +88,8 @@ constexpr float A2_THR = 8.0f;
 struct Ph0 { static constexpr int value = 0; };
 struct Ph1 { static constexpr int value = 1; };
 
-__global__ __launch_bounds__(256, WIW_A32_WAVES) void attn_spatial32_kernel(const uint16_t* __restrict__ QK, int ldqk, int k_col_off,
+// 3 waves per SIMD is what the register budget is cut for (168 VGPRs, no spill; 2, i.e. 256 VGPRs, measured 2 % slower)
+__global__ __launch_bounds__(256, 3) void attn_spatial32_kernel(const uint16_t* __restrict__ QK, int ldqk, int k_col_off,
                                                                 const uint16_t* __restrict__ Vt, int64_t ldvt,
                                                                 uint16_t* __restrict__ O, int ldo, int S, int heads, int q_tiles) {
     __shared__ __attribute__((aligned(16))) char smem[A2_NSTAGE * A2_STAGE];

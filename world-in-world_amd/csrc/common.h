@@ -60,12 +60,9 @@ WIW_DEV float silu_f(float x) {   // x * sigmoid(x) on the raw v_exp_f32 / v_rcp
 // Round 5: Phi(x) = sigmoid(x * P(min(|x|, 6))) with P of degree 4 fitted (minimax on the absolute error of
 // x * Phi(x) over the whole line, /tmp-free recipe in oracle/gelu_fit.py) — |error| <= 5.2e-6 evaluated in fp32 with the raw
 // v_exp_f32 / v_rcp_f32, i.e. 1/50 of half an fp16 ulp at |h| = 1 and 1/400 of bf16's; 10 VALU instructions instead of the
-// 14 of Abramowitz-Stegun 7.1.26 (|error| <= 1.5e-7), which stays as gelu_erf_as_f: the fine-tuning kernels (train.hip) keep
-// it, and -DWIW_GELU_AS7126=1 builds every epilogue with it (the A/B switch).  The GEGLU epilogues evaluate 20480 of these
-// per 256x160 block tile and their VALU issue time is NOT hidden behind MFMAs.  The coefficients carry -log2(e).
-#ifndef WIW_GELU_AS7126
-#define WIW_GELU_AS7126 0
-#endif
+// 14 of Abramowitz-Stegun 7.1.26 (|error| <= 1.5e-7), which stays as gelu_erf_as_f for the fine-tuning kernels (train.hip) only.
+// The GEGLU epilogues evaluate 20480 of these per 256x160 block tile and their VALU issue time is NOT hidden behind MFMAs.
+// The coefficients carry -log2(e).
 #define WIW_GELU_C0 (-2.3031814098358154f)
 #define WIW_GELU_C1 (0.0026162799913436174f)
 #define WIW_GELU_C2 (-0.1058432012796402f)
@@ -88,19 +85,15 @@ WIW_DEV float gelu_erf_as_f(float x) {
     return 0.5f * __builtin_fmaf(ax, erf_abs, x);
 }
 WIW_DEV float gelu_erf_f(float x) {
-#if WIW_GELU_AS7126
-    return gelu_erf_as_f(x);
-#else
     const float a = __builtin_fminf(fabsf(x), WIW_GELU_CLAMP);     // beyond 6: x * sigmoid(3.3 x) is x or 0 to fp32 roundoff
     float p = __builtin_fmaf(WIW_GELU_C4, a, WIW_GELU_C3);
     p = __builtin_fmaf(p, a, WIW_GELU_C2);
     p = __builtin_fmaf(p, a, WIW_GELU_C1);
     p = __builtin_fmaf(p, a, WIW_GELU_C0);
     return x * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(x * p));     // exp2 -> inf for x << 0: rcp(inf) = 0
-#endif
 }
 
-// gelu_erf_f on NP PACKED pairs at once, breadth first, the same arithmetic bit for bit (both forms).  One wave issues at most one VALU
+// gelu_erf_f on NP PACKED pairs at once, breadth first, the same arithmetic bit for bit.  One wave issues at most one VALU
 // instruction per ~5.4 cycles (8.5 when it depends on the previous one) packed or not (tools/ubench/valu_rate.hip), so the
 // cost of a GELU block is its instruction count: v_pk_* halves it and independent work per stage removes the dependency
 // stalls.  wiw_regp is an empty asm statement that reads and writes every pair of a stage — without it instruction
@@ -118,7 +111,6 @@ WIW_DEV void wiw_regp(wiw_f32x2 (&a)[NP]) {
 }
 template <int NP>
 WIW_DEV void gelu_erf_pk(wiw_f32x2 (&x)[NP]) {
-#if !WIW_GELU_AS7126
     wiw_f32x2 a[NP], p[NP];
     const auto fma2s = [](wiw_f32x2 a_, wiw_f32x2 b_, wiw_f32x2 c_) { return __builtin_elementwise_fma(a_, b_, c_); };
     const auto bcs = [](float c) { return wiw_f32x2{c, c}; };
@@ -151,48 +143,6 @@ WIW_DEV void gelu_erf_pk(wiw_f32x2 (&x)[NP]) {
     wiw_regp(p);
 #pragma unroll
     for (int i = 0; i < NP; ++i) x[i] = x[i] * p[i];
-    wiw_regp(x);
-    return;
-#endif
-
-    wiw_f32x2 ax[NP], z[NP], t[NP], e[NP], poly[NP];
-    const auto fma2 = [](wiw_f32x2 a, wiw_f32x2 b, wiw_f32x2 c) { return __builtin_elementwise_fma(a, b, c); };
-    const auto bc = [](float c) { return wiw_f32x2{c, c}; };
-#pragma unroll
-    for (int i = 0; i < NP; ++i) {
-        ax[i] = wiw_f32x2{fabsf(x[i].x), fabsf(x[i].y)};
-        z[i] = ax[i] * 0.70710678118654752f;
-    }
-    wiw_regp(z);
-#pragma unroll
-    for (int i = 0; i < NP; ++i) { t[i] = fma2(bc(0.3275911f), z[i], bc(1.0f)); e[i] = (z[i] * -1.4426950408889634f) * z[i]; }
-    wiw_regp(t); wiw_regp(e);
-#pragma unroll
-    for (int i = 0; i < NP; ++i) {
-        t[i] = wiw_f32x2{__builtin_amdgcn_rcpf(t[i].x), __builtin_amdgcn_rcpf(t[i].y)};
-        e[i] = wiw_f32x2{__builtin_amdgcn_exp2f(e[i].x), __builtin_amdgcn_exp2f(e[i].y)};
-    }
-    wiw_regp(t); wiw_regp(e);
-#pragma unroll
-    for (int i = 0; i < NP; ++i) poly[i] = fma2(bc(1.061405429f), t[i], bc(-1.453152027f));
-    wiw_regp(poly);
-#pragma unroll
-    for (int i = 0; i < NP; ++i) poly[i] = fma2(poly[i], t[i], bc(1.421413741f));
-    wiw_regp(poly);
-#pragma unroll
-    for (int i = 0; i < NP; ++i) poly[i] = fma2(poly[i], t[i], bc(-0.284496736f));
-    wiw_regp(poly);
-#pragma unroll
-    for (int i = 0; i < NP; ++i) poly[i] = fma2(poly[i], t[i], bc(0.254829592f));
-    wiw_regp(poly);
-#pragma unroll
-    for (int i = 0; i < NP; ++i) poly[i] = -poly[i] * t[i];
-    wiw_regp(poly);
-#pragma unroll
-    for (int i = 0; i < NP; ++i) poly[i] = fma2(poly[i], e[i], bc(1.0f));     // erf|x|
-    wiw_regp(poly);
-#pragma unroll
-    for (int i = 0; i < NP; ++i) x[i] = fma2(ax[i], poly[i], x[i]) * 0.5f;
     wiw_regp(x);
 }
 

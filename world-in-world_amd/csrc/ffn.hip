@@ -23,6 +23,15 @@
 // (next tile's X loads are issued under the last GEGLU), the Y-waves' epilogue (bias, per-frame vector, residuals,
 // 16-byte streaming stores through a per-wave LDS transpose) happens once per 629 MFLOP instead of once per 26.
 // One block barrier per slot; 6 slots per chunk: 5 K tiles + the GEGLU / phase-2 slot.
+// Round 6 schedule (the per-K-tile schedule of rounds 3-5 lost each comparison at M = 258 048):
+//   * the Y-waves issue ALL five W1 K tiles of the next chunk in slot 5, in front of their phase-2 MFMAs and under the
+//     H-waves' GEGLU, instead of one tile per K-tile slot: 648-654 -> 628-634 us (profiles/r19f_ffn_dma_schedules.txt);
+//   * with the chunk's W1 resident before its first K tile is read, the H-waves run the K phase WITHOUT per-K-tile block
+//     barriers: two barriers per chunk (A: W1 resident / W2 buffer and ring hand-over; B: W2 + bias landed, H of the
+//     previous chunk visible) instead of six: 634-646 -> 615-620 us (profiles/r19g_ffn_freek.txt; timelines r19h);
+//   * the up-projection's accumulators START at the bias (b1's chunk goes out with the bulk W1 tiles and is resident at
+//     barrier A) instead of at zero: the GEGLU loses its 32 bias adds per lane and chunk (of ~300 VALU issues):
+//     620-622 -> 606-612 us (profiles/r20g_ffn_bias_init.txt).
 //
 // Weights: W1 packed [2560][320] in chunks of 128 rows = [64 value | 64 gate] and W2 [320][1280], both in the tiled
 // layout of wiw_gemm_bf16 (1-KiB blocks, chunks pre-swizzled): one DMA instruction copies one contiguous KiB and the LDS
@@ -33,45 +42,14 @@
 #include <type_traits>
 
 #include "common.h"
-
-#ifndef FFN_P2_PRIO
-#define FFN_P2_PRIO 0   // s_setprio of the Y-waves' phase-2 MFMA stream (A/B knob)
-#endif
-#ifndef FFN_GE_PRIO
-#define FFN_GE_PRIO 0   // s_setprio of the H-waves' GEGLU segment (A/B knob)
-#endif
-#ifndef FFN_W1_BULK
-#define FFN_W1_BULK 1   // 1 (round 6): the Y-waves issue ALL five W1 K tiles of the next chunk in slot 5 (in front of their phase-2
-                        // MFMAs, while the H-waves evaluate the GEGLU) instead of one tile per K-tile slot: 648-654 -> 628-634 us at
-                        // M = 258 048 (profiles/r19f_ffn_dma_schedules.txt); 0 = the schedule of rounds 3-5 (A/B knob)
-#endif
-#ifndef FFN_FREE_K
-#define FFN_FREE_K 1    // (needs FFN_W1_BULK) 1 (round 6): with a chunk's five W1 K tiles resident before its first K tile is read, the
-                        // H-waves run the K phase WITHOUT the per-K-tile block barriers: two barriers per chunk (A: W1 resident /
-                        // W2 buffer and ring hand-over; B: W2 + bias landed, H of the previous chunk visible) instead of six:
-                        // 634-646 -> 615-620 us at M = 258 048 (profiles/r19g_ffn_freek.txt; timelines r19h); 0 = A/B knob
-#endif
-static_assert(!FFN_FREE_K || FFN_W1_BULK, "FFN_FREE_K needs the bulk W1 schedule");
-#ifndef FFN_BIAS_INIT
-#define FFN_BIAS_INIT FFN_FREE_K   // (needs FFN_FREE_K) 1 (round 6): the up-projection's accumulators START at the bias (b1's chunk is
-                                   // resident before the chunk's K phase: the Y-waves issue it with the bulk W1 tiles) instead of at
-                                   // zero — the GEGLU loses its 32 bias adds per lane and chunk (of ~300 VALU issues); 0 = A/B knob
-#endif
-static_assert(!FFN_BIAS_INIT || FFN_FREE_K, "FFN_BIAS_INIT needs the free-running K phase (bias resident at barrier A)");
-#ifndef FFN_ABLATE
-#define FFN_ABLATE 0   // timing-only builds (tools/build_variant.py): 1 no GELU math, 2 no phase-2 MFMAs, 3 no LDS-DMA, 4 no phase-1 MFMAs
-#endif
+#include "lds_dma.h"
 
 namespace {
 
 constexpr int C = 320, HID = 1280, HC = 64, NCH = HID / HC;      // 20 hidden chunks
 constexpr int BM = 128, BK = 64, NKT = C / BK;                   // 5 K tiles per chunk
 constexpr int KS = C / 32;                                       // 10 k-steps of 32 over X's K
-#ifndef FFN_RING
-#define FFN_RING 5
-#endif
-constexpr int RING_STAGES = FFN_RING;
-[[maybe_unused]] constexpr int LEAD = RING_STAGES - 1;     // W1 K tiles: issued LEAD slots before they are read
+constexpr int RING_STAGES = 5;                                   // W1 ring: the five K tiles of one chunk are resident at once
 constexpr int RING_STAGE_BYTES = 2 * HC * BK * 2;                 // one W1 K tile: 128 rows x 64 k = 16 KiB
 constexpr int W2_OFF = RING_STAGES * RING_STAGE_BYTES;           // 81920
 constexpr int W2_BYTES = C * HC * 2;                             // 320 rows x 64 k = 40 KiB
@@ -89,84 +67,13 @@ constexpr int STG_ROWB = 336;                                    // epilogue sta
 constexpr int STG_WAVE = 16 * STG_ROWB;                          // 5376 B per Y-wave, inside the W2 buffer
 static_assert(4 * STG_WAVE <= W2_BYTES, "epilogue staging must fit in the W2 buffer");
 
-typedef const __attribute__((address_space(1))) void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
-// LDS-DMA (16 bytes per lane, LDS destination = wave-uniform base + 16 * lane) as INLINE ASM: hipcc models the builtin as a
-// FLAT access that may touch LDS, and while one is pending every compiler-inserted wait for a ds_read is lgkmcnt(0) — the
-// Y-waves' software-pipelined fragment reads of phase 2 (8 in flight) would drain at every use.  The asm form is invisible to
-// that bookkeeping: its completion is counted by hand (wait_vmcnt below), exactly as for the builtin.  M0 carries the LDS
-// address and is saved / restored inside the statement (the compiler does not preserve it around asm).
-WIW_DEV void glds16(const char* g, char* l) {
-#if FFN_ABLATE == 3
-    asm volatile("" ::"v"(g), "s"(l));
-    return;
-#endif
-    const uint32_t lds = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(lptr_t)l);
-    uint32_t keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(g), "s"(lds) : "memory");
-}
 // X rows and residual rows are read exactly once by the whole launch: streaming (nt) loads, so that they do not evict the
-// 2.4 MB of weights every CU of the XCD re-reads from its L2 for every tile (A/B knob FFN_PLAIN_LOADS)
+// 2.4 MB of weights every CU of the XCD re-reads from its L2 for every tile
 template <typename T>
 WIW_DEV T ld_stream(const T* p) {
-#ifdef FFN_PLAIN_LOADS
-    return *p;
-#else
     typedef int i32x4_t __attribute__((ext_vector_type(4)));
     static_assert(sizeof(T) == 16, "16-byte loads");
     return __builtin_bit_cast(T, __builtin_nontemporal_load((const i32x4_t*)p));
-#endif
-}
-template <int N>
-WIW_DEV void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-WIW_DEV void wait_vmcnt_rt(int n) {   // wave-uniform n (s_waitcnt takes an immediate)
-    switch (n) {
-        case 0: wait_vmcnt<0>(); break;
-        case 1: wait_vmcnt<1>(); break;
-        case 2: wait_vmcnt<2>(); break;
-        case 3: wait_vmcnt<3>(); break;
-        case 4: wait_vmcnt<4>(); break;
-        case 5: wait_vmcnt<5>(); break;
-        case 6: wait_vmcnt<6>(); break;
-        case 7: wait_vmcnt<7>(); break;
-        case 8: wait_vmcnt<8>(); break;
-        case 9: wait_vmcnt<9>(); break;
-        case 10: wait_vmcnt<10>(); break;
-        case 11: wait_vmcnt<11>(); break;
-        case 12: wait_vmcnt<12>(); break;
-        case 13: wait_vmcnt<13>(); break;
-        case 14: wait_vmcnt<14>(); break;
-        case 15: wait_vmcnt<15>(); break;
-        case 16: wait_vmcnt<16>(); break;
-        case 17: wait_vmcnt<17>(); break;
-        case 18: wait_vmcnt<18>(); break;
-        case 19: wait_vmcnt<19>(); break;
-        case 20: wait_vmcnt<20>(); break;
-        case 21: wait_vmcnt<21>(); break;
-        case 22: wait_vmcnt<22>(); break;
-        case 23: wait_vmcnt<23>(); break;
-        case 24: wait_vmcnt<24>(); break;
-        case 25: wait_vmcnt<25>(); break;
-        case 26: wait_vmcnt<26>(); break;
-        case 27: wait_vmcnt<27>(); break;
-        case 28: wait_vmcnt<28>(); break;
-        case 29: wait_vmcnt<29>(); break;
-        case 30: wait_vmcnt<30>(); break;
-        default: wait_vmcnt<31>(); break;
-    }
-}
-WIW_DEV void wave_lds_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-WIW_DEV void slot_barrier() {   // this wave's LDS accesses are retired, then rendezvous of all 8 waves
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
 }
 
 #ifdef WIW_FFN_TRACE   // debug build: block 0 stamps s_memtime at the slot boundaries of two steady-state chunks (waves 0 and 4)
@@ -184,96 +91,49 @@ constexpr int TR_CC0 = 23, TR_NCC = 2;   // chunks 3 and 4 of the block's second
 #define FTP(role, idx) do { } while (0)
 #endif
 
-// gelu_erf_f of common.h (exact-erf GELU, Abramowitz-Stegun 7.1.26, same arithmetic bit for bit) on EIGHT values as four
-// PACKED pairs, breadth first.  Why (tools/ubench/valu_rate.hip, tools/ffn_trace.py): one wave issues at most one VALU
-// instruction per ~5.4 cycles (8.5 when it depends on the previous one, ~9 for v_exp / v_rcp) whether it is packed or not
+// gelu_erf_f of common.h (the fitted sigmoid form of the erf GELU, same arithmetic bit for bit; 13 instead of the 18 issues
+// per pair of Abramowitz-Stegun 7.1.26) on SIXTEEN values as eight PACKED pairs, breadth first.  Why
+// (tools/ubench/valu_rate.hip, tools/ffn_trace.py): one wave issues at most one VALU instruction per ~5.4 cycles (8.5 when it depends on the previous one, ~9 for v_exp / v_rcp) whether it is packed or not
 // and whether or not a second wave shares the SIMD — so the cost of the GEGLU is its INSTRUCTION COUNT times 5.4 if every
 // stage has independent work, and v_pk_* halves the count.  Evaluated value by value (a loop over gelu_erf_f) the 32
 // values of a wave took 3.8 k cycles, dependent-chain-bound.
 //   REGP8: an empty asm statement that reads and writes the eight pairs of a stage — every pair exists in its own registers
 //   there and nothing of the next stage can be computed before it (source order and sched_barrier do not survive
 //   instruction selection for pure arithmetic).
-typedef float f32x2_t __attribute__((ext_vector_type(2)));
 #define REGP8(a) asm volatile("" : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]), "+v"(a[4]), "+v"(a[5]), "+v"(a[6]), "+v"(a[7]))
-WIW_DEV f32x2_t pk_fma(f32x2_t a, f32x2_t b, f32x2_t c) { return __builtin_elementwise_fma(a, b, c); }
 WIW_DEV void gelu_erf16(float (&x)[16]) {   // 8 packed pairs per stage: a stage's issue time (~45 cycles) covers a packed result's latency
-#if !WIW_GELU_AS7126
-    {   // round 5: the sigmoid form of common.h's gelu_erf_f, the same arithmetic bit for bit (13 instead of 18 issues per pair)
-        f32x2_t xv[8], a[8], p[8];
-        const auto bc = [](float c) { return f32x2_t{c, c}; };
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            xv[i] = f32x2_t{x[2 * i], x[2 * i + 1]};
-            a[i] = f32x2_t{__builtin_fminf(fabsf(x[2 * i]), WIW_GELU_CLAMP), __builtin_fminf(fabsf(x[2 * i + 1]), WIW_GELU_CLAMP)};
-            p[i] = pk_fma(bc(WIW_GELU_C4), a[i], bc(WIW_GELU_C3));
-        }
-        REGP8(p);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) p[i] = pk_fma(p[i], a[i], bc(WIW_GELU_C2));
-        REGP8(p);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) p[i] = pk_fma(p[i], a[i], bc(WIW_GELU_C1));
-        REGP8(p);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) p[i] = pk_fma(p[i], a[i], bc(WIW_GELU_C0));
-        REGP8(p);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) p[i] = xv[i] * p[i];
-        REGP8(p);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) p[i] = f32x2_t{__builtin_amdgcn_exp2f(p[i].x), __builtin_amdgcn_exp2f(p[i].y)};
-        REGP8(p);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) p[i] = p[i] + bc(1.0f);
-        REGP8(p);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) p[i] = f32x2_t{__builtin_amdgcn_rcpf(p[i].x), __builtin_amdgcn_rcpf(p[i].y)};
-        REGP8(p);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) xv[i] = xv[i] * p[i];
-        REGP8(xv);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) { x[2 * i] = xv[i].x; x[2 * i + 1] = xv[i].y; }
-        return;
-    }
-#endif
-    f32x2_t xv[8], ax[8], z[8], t[8], e[8], poly[8];
+    wiw_f32x2 xv[8], a[8], p[8];
+    const auto bc = [](float c) { return wiw_f32x2{c, c}; };
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
-        xv[i] = f32x2_t{x[2 * i], x[2 * i + 1]};
-        ax[i] = f32x2_t{fabsf(x[2 * i]), fabsf(x[2 * i + 1])};
-        z[i] = ax[i] * 0.70710678118654752f;
+        xv[i] = wiw_f32x2{x[2 * i], x[2 * i + 1]};
+        a[i] = wiw_f32x2{__builtin_fminf(fabsf(x[2 * i]), WIW_GELU_CLAMP), __builtin_fminf(fabsf(x[2 * i + 1]), WIW_GELU_CLAMP)};
+        p[i] = pk_fma(bc(WIW_GELU_C4), a[i], bc(WIW_GELU_C3));
     }
-    REGP8(z);
+    REGP8(p);
 #pragma unroll
-    for (int i = 0; i < 8; ++i) { t[i] = pk_fma(f32x2_t{0.3275911f, 0.3275911f}, z[i], f32x2_t{1.0f, 1.0f}); e[i] = (z[i] * -1.4426950408889634f) * z[i]; }
-    REGP8(t); REGP8(e);
+    for (int i = 0; i < 8; ++i) p[i] = pk_fma(p[i], a[i], bc(WIW_GELU_C2));
+    REGP8(p);
 #pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        t[i] = f32x2_t{__builtin_amdgcn_rcpf(t[i].x), __builtin_amdgcn_rcpf(t[i].y)};
-        e[i] = f32x2_t{__builtin_amdgcn_exp2f(e[i].x), __builtin_amdgcn_exp2f(e[i].y)};
-    }
-    REGP8(t); REGP8(e);
+    for (int i = 0; i < 8; ++i) p[i] = pk_fma(p[i], a[i], bc(WIW_GELU_C1));
+    REGP8(p);
 #pragma unroll
-    for (int i = 0; i < 8; ++i) poly[i] = pk_fma(f32x2_t{1.061405429f, 1.061405429f}, t[i], f32x2_t{-1.453152027f, -1.453152027f});
-    REGP8(poly);
+    for (int i = 0; i < 8; ++i) p[i] = pk_fma(p[i], a[i], bc(WIW_GELU_C0));
+    REGP8(p);
 #pragma unroll
-    for (int i = 0; i < 8; ++i) poly[i] = pk_fma(poly[i], t[i], f32x2_t{1.421413741f, 1.421413741f});
-    REGP8(poly);
+    for (int i = 0; i < 8; ++i) p[i] = xv[i] * p[i];
+    REGP8(p);
 #pragma unroll
-    for (int i = 0; i < 8; ++i) poly[i] = pk_fma(poly[i], t[i], f32x2_t{-0.284496736f, -0.284496736f});
-    REGP8(poly);
+    for (int i = 0; i < 8; ++i) p[i] = wiw_f32x2{__builtin_amdgcn_exp2f(p[i].x), __builtin_amdgcn_exp2f(p[i].y)};
+    REGP8(p);
 #pragma unroll
-    for (int i = 0; i < 8; ++i) poly[i] = pk_fma(poly[i], t[i], f32x2_t{0.254829592f, 0.254829592f});
-    REGP8(poly);
+    for (int i = 0; i < 8; ++i) p[i] = p[i] + bc(1.0f);
+    REGP8(p);
 #pragma unroll
-    for (int i = 0; i < 8; ++i) poly[i] = -poly[i] * t[i];
-    REGP8(poly);
+    for (int i = 0; i < 8; ++i) p[i] = wiw_f32x2{__builtin_amdgcn_rcpf(p[i].x), __builtin_amdgcn_rcpf(p[i].y)};
+    REGP8(p);
 #pragma unroll
-    for (int i = 0; i < 8; ++i) poly[i] = pk_fma(poly[i], e[i], f32x2_t{1.0f, 1.0f});     // erf|x|
-    REGP8(poly);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) xv[i] = pk_fma(ax[i], poly[i], xv[i]) * 0.5f;
+    for (int i = 0; i < 8; ++i) xv[i] = xv[i] * p[i];
     REGP8(xv);
 #pragma unroll
     for (int i = 0; i < 8; ++i) { x[2 * i] = xv[i].x; x[2 * i + 1] = xv[i].y; }
@@ -425,18 +285,10 @@ __global__ __launch_bounds__(512, 2) void ffn_kernel(const FfnArgs p) {
             for (int ni = 0; ni < 8; ++ni) fb[ni] = *(const bf16x8*)(s + ni * 2048);
         };
         auto mma1 = [&](const bf16x8& f, const bf16x8& x0, const bf16x8& x1, int ni) {   // one W1 fragment x both row blocks
-#if FFN_ABLATE == 4
-            asm volatile("" ::"v"(f), "v"(x0), "v"(x1));
-            return;
-#endif
             acc[0][ni] = WIW_MFMA(f, x0, acc[0][ni]);
             acc[1][ni] = WIW_MFMA(f, x1, acc[1][ni]);
         };
         auto mma = [&](const bf16x8* fb, const bf16x8& x0, const bf16x8& x1) {
-#if FFN_ABLATE == 4
-            asm volatile("" ::"v"(fb[0]), "v"(fb[7]), "v"(x0), "v"(x1));
-            return;
-#endif
             __builtin_amdgcn_s_setprio(1);
 #pragma unroll
             for (int ni = 0; ni < 8; ++ni) {
@@ -453,20 +305,13 @@ __global__ __launch_bounds__(512, 2) void ffn_kernel(const FfnArgs p) {
         // one hidden chunk (H-wave side); LAST: compile-time "chunk NCH - 1 of its tile" (F32X only, see the loads below)
         auto chunk = [&](const int cc, auto last_tag) {
             constexpr bool LAST = decltype(last_tag)::value;
-#if !FFN_BIAS_INIT
-#pragma unroll
-            for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-                for (int ni = 0; ni < 8; ++ni) acc[mi][ni] = f32x4{0.f, 0.f, 0.f, 0.f};
-#endif
             // ---- slots 0..4: K tile kt.  The MFMAs of a K tile's second k-step run in the NEXT slot, under that slot's
             // first fragment reads, so the matrix pipe is not idle while a slot's first reads are in flight.
 #pragma unroll
             for (int kt = 0; kt < NKT; ++kt) {
                 FTP(0, 2 * kt);          // end of the previous slot's work
-                if (!FFN_FREE_K || kt == 0) slot_barrier();
+                if (kt == 0) slot_barrier();
                 FTP(0, 2 * kt + 1);      // barrier passed
-#if FFN_BIAS_INIT
                 if (kt == 0) {   // behind barrier A the chunk's bias is resident: both row blocks start at it (a lane's 4 columns)
                     const char* bs0 = smem + BIAS_OFF + (cc & 1) * BIAS_BYTES + fq * 16;
 #pragma unroll
@@ -476,7 +321,6 @@ __global__ __launch_bounds__(512, 2) void ffn_kernel(const FfnArgs p) {
                         acc[1][ni] = f32x4{b.x, b.y, b.z, b.w};
                     }
                 }
-#endif
                 // two halves of [2 MFMAs | 1 ds_read_b128] x 8, order pinned: the first half runs the PENDING k-step (fragments
                 // fbB of the previous slot) while this K tile's k-step-0 fragments arrive, the second half runs k-step 0 while
                 // the k-step-1 fragments arrive — the reads' issue slots sit inside the MFMAs' pipe time (left alone the
@@ -519,36 +363,21 @@ __global__ __launch_bounds__(512, 2) void ffn_kernel(const FfnArgs p) {
             } else {
                 if (c == NCH - 1 && ti + 1 < ntl) load_x(blockIdx.x + (ti + 1) * nb);
             }
-            if (FFN_GE_PRIO) __builtin_amdgcn_s_setprio(FFN_GE_PRIO);
             {
-                const char* bs = smem + BIAS_OFF + (cc & 1) * BIAS_BYTES;
                 char* hb = smem + H_OFF + (cc & 1) * H_BYTES;
 #pragma unroll
                 for (int np = 0; np < 2; ++np) {      // two 16-column fragments (ni = 2*np, 2*np + 1) per pass: 16 gate values
-                    float4 bv[2], bg[2];
                     float g16[16];
 #pragma unroll
                     for (int h = 0; h < 2; ++h) {
                         const int ni = 2 * np + h;
-#if FFN_BIAS_INIT
-                        (void)bs; bv[h] = bg[h] = float4{0.f, 0.f, 0.f, 0.f};      // the accumulators carry the bias already
+                        // (the accumulators carry the bias already)
 #pragma unroll
                         for (int mi = 0; mi < 2; ++mi)
 #pragma unroll
                             for (int r = 0; r < 4; ++r) g16[h * 8 + mi * 4 + r] = acc[mi][ni + 4][r];
-#else
-                        bv[h] = *(const float4*)(bs + (ni * 16 + fq * 4) * 4);
-                        bg[h] = *(const float4*)(bs + (HC + ni * 16 + fq * 4) * 4);
-#pragma unroll
-                        for (int mi = 0; mi < 2; ++mi) {
-                            g16[h * 8 + mi * 4 + 0] = acc[mi][ni + 4][0] + bg[h].x; g16[h * 8 + mi * 4 + 1] = acc[mi][ni + 4][1] + bg[h].y;
-                            g16[h * 8 + mi * 4 + 2] = acc[mi][ni + 4][2] + bg[h].z; g16[h * 8 + mi * 4 + 3] = acc[mi][ni + 4][3] + bg[h].w;
-                        }
-#endif
                     }
-#if FFN_ABLATE != 1
                     gelu_erf16(g16);
-#endif
 #pragma unroll
                     for (int h = 0; h < 2; ++h) {
                         const int ni = 2 * np + h;
@@ -557,13 +386,8 @@ __global__ __launch_bounds__(512, 2) void ffn_kernel(const FfnArgs p) {
                             const f32x4 v = acc[mi][ni];
                             const float* g = g16 + h * 8 + mi * 4;
                             uint2 pk;
-#if FFN_BIAS_INIT
                             pk.x = pack2bf(v[0] * g[0], v[1] * g[1]);
                             pk.y = pack2bf(v[2] * g[2], v[3] * g[3]);
-#else
-                            pk.x = pack2bf((v[0] + bv[h].x) * g[0], (v[1] + bv[h].y) * g[1]);
-                            pk.y = pack2bf((v[2] + bv[h].z) * g[2], (v[3] + bv[h].w) * g[3]);
-#endif
                             // H[row][16*ni + 4*fq .. +3]: 16-byte chunk 2*ni + (fq >> 1) of the row, swizzled like every K tile
                             const int row = wq * 32 + mi * 16 + frow;
                             *(uint2*)(hb + row * 128 + (((2 * ni + (fq >> 1)) ^ (frow & 7)) << 4) + (fq & 1) * 8) = pk;
@@ -572,7 +396,6 @@ __global__ __launch_bounds__(512, 2) void ffn_kernel(const FfnArgs p) {
                     FTP(0, 20 + np);
                 }
             }
-            if (FFN_GE_PRIO) __builtin_amdgcn_s_setprio(0);
             if constexpr (F32X && LAST) load_xf(xf1, blockIdx.x + (ti + 1) * nb, 1);
             FTP(0, 13);              // GEGLU done, H written
             // tile-end barrier: in this iteration the Y-waves finished a tile (its last chunk is cc - 1) and stage its
@@ -597,7 +420,7 @@ __global__ __launch_bounds__(512, 2) void ffn_kernel(const FfnArgs p) {
         }
         // drain: the Y-waves finish the last chunk (+ the tile-end barrier, see above)
 #pragma unroll
-        for (int i = 0; i < (FFN_FREE_K ? 3 : NKT + 2); ++i) slot_barrier();
+        for (int i = 0; i < 3; ++i) slot_barrier();
 #ifdef WIW_FFN_TRACE
         if (trace_blk) for (int i = 0; i < 64; ++i) g_ftrace[0][i] = *(volatile long long*)(smem + SMEM + i * 8);
 #endif
@@ -619,47 +442,29 @@ __global__ __launch_bounds__(512, 2) void ffn_kernel(const FfnArgs p) {
             const char* src = W1b + ((int64_t)((ld_c * 16 + wq * 4) * NKT + ld_kt)) * 1024 + lane * 16;
             char* dst = smem + ld_st * RING_STAGE_BYTES + wq * 4096;
 #pragma unroll
-            for (int i = 0; i < 4; ++i) glds16(src + (int64_t)i * NKT * 1024, dst + i * 1024);
+            for (int i = 0; i < 4; ++i) glds16_asm(src + (int64_t)i * NKT * 1024, dst + i * 1024);
             if (++ld_kt == NKT) { ld_kt = 0; ld_c = ld_c + 1 == NCH ? 0 : ld_c + 1; }
             ld_st = ld_st + 1 == RING_STAGES ? 0 : ld_st + 1;
             --ld_left;
         };
-#if FFN_W1_BULK
-        // prologue: the five W1 K tiles of chunk 0; tile 0 has landed when <= 16 instructions are outstanding
+        // prologue: the five W1 K tiles of chunk 0
 #pragma unroll
         for (int i = 0; i < NKT; ++i) issue_w1();
-#if FFN_BIAS_INIT
         // ... and the bias of chunk 0: the H-waves' accumulators start at it (behind barrier A)
-        if (lane < 8) glds16((const char*)p.b1 + wq * 128 + lane * 16, smem + BIAS_OFF + wq * 128);
-#endif
-        wait_vmcnt<FFN_FREE_K ? 0 : 4 * (NKT - 1)>();
-        int h1 = 0, h2 = 0;
-#else
-        // prologue: K tiles 0 .. LEAD-1 (NC >= 20 chunks: they exist); tile 0 has landed when <= 4 * (LEAD - 1) are outstanding
-#pragma unroll
-        for (int i = 0; i < LEAD; ++i) issue_w1();
-        wait_vmcnt<4 * (LEAD - 1)>();
-        int h1 = LEAD >= 3 ? 4 : 0, h2 = LEAD >= 4 ? 4 : 0;   // DMA instructions issued in the previous two DMA slots (prologue tiles)
-#endif
+        if (lane < 8) glds16_asm((const char*)p.b1 + wq * 128 + lane * 16, smem + BIAS_OFF + wq * 128);
+        wait_vmcnt<0>();
 
         const int sw0 = (fq ^ (frow & 7)) << 4, sw1 = ((4 + fq) ^ (frow & 7)) << 4;
         int c = 0;   // chunk (inside its tile) the H-waves work on in this iteration; this wave works on chunk c - 1
         int ti = 0;  // tile counter of the chunk THIS wave works on
         for (int cc = 0; cc <= NC; ++cc) {
             const int c2 = c == 0 ? NCH - 1 : c - 1;   // chunk of phase 2 in this iteration (valid for cc >= 1)
-#if FFN_FREE_K
             // ---- K phase of the H-waves (they free-run through the chunk's five resident W1 K tiles): behind barrier A — every
             // Y-wave is through phase 2 of the previous iteration, the W2 buffer is free — this wave issues its share of W2
             // chunk c2 (10 blocks) and of the bias chunk, confirms them, and meets the H-waves at barrier B
             FTP(1, 0);
             slot_barrier();
             FTP(1, 1);
-#if !FFN_BIAS_INIT
-            if (cc < NC) {
-                if (lane < 8) glds16((const char*)p.b1 + c * (2 * HC * 4) + wq * 128 + lane * 16,
-                                     smem + BIAS_OFF + (cc & 1) * BIAS_BYTES + wq * 128);
-            }
-#endif
             if (cc >= 1) {
 #pragma unroll
                 for (int g = 0; g < 3; ++g) {
@@ -670,68 +475,14 @@ __global__ __launch_bounds__(512, 2) void ffn_kernel(const FfnArgs p) {
                     char* dst = smem + W2_OFF + rb * 1024;
 #pragma unroll
                     for (int i = 0; i < 4; ++i)
-                        if (i < NB2) glds16(src + (int64_t)i * NCH * 1024, dst + i * 1024);
+                        if (i < NB2) glds16_asm(src + (int64_t)i * NCH * 1024, dst + i * 1024);
                 }
             }
             FTP(1, 2);
             wait_vmcnt<0>();
-            (void)h1; (void)h2;
-#else
-#pragma unroll
-            for (int kt = 0; kt < NKT; ++kt) {
-                FTP(1, 3 * kt);          // end of the previous slot's work
-                slot_barrier();
-                FTP(1, 3 * kt + 1);      // barrier passed
-                // The W1 K tile the H-waves read in slot d + 1 was issued LEAD - 1 = 3 DMA slots before slot d: at the end of a
-                // slot only what was issued more than two slots ago has to have landed (an LDS-DMA takes ~1.5 k cycles from
-                // issue to landed under this kernel's load: with a two-slot lead every slot ended in a 200-350 cycle vmcnt
-                // wait, tools/ffn_trace.py).  W2 chunk c2 (40 blocks of 1 KiB, consumed in slot 5) goes out in slots 0..2 as
-                // 4 | 3 | 3 blocks per wave (slot 4 therefore waits for everything older than ONE slot), the bias chunk of the
-                // H-waves' current chunk (512 B, read by them in slot 5) as 128 B per wave in slot 0.
-                int h0 = 0;
-                if (kt == 0 && cc < NC) {
-                    if (lane < 8) glds16((const char*)p.b1 + c * (2 * HC * 4) + wq * 128 + lane * 16,
-                                         smem + BIAS_OFF + (cc & 1) * BIAS_BYTES + wq * 128);
-                    h0 += 1;
-                }
-                if (cc >= 1 && kt < 3) {
-                    // (spreading the W2 pieces 3|3|2|2 or 2 x 5 over the slots, or the bulk W1 issue BEHIND phase 2: measured, no
-                    // gain — profiles/r19f_ffn_dma_schedules.txt)
-                    const int NB2 = kt == 0 ? 4 : 3;              // blocks per wave in this slot (kt is unrolled)
-                    const int RB0 = kt == 0 ? 0 : 16 + (kt - 1) * 12;   // first block of this slot: 0 | 16 | 28
-                    const int rb = RB0 + wq * NB2;
-                    const char* src = W2b + ((int64_t)rb * NCH + c2) * 1024 + lane * 16;
-                    char* dst = smem + W2_OFF + rb * 1024;
-#pragma unroll
-                    for (int i = 0; i < 4; ++i)
-                        if (i < NB2) glds16(src + (int64_t)i * NCH * 1024, dst + i * 1024);
-                    h0 += NB2;
-                }
-#if FFN_W1_BULK
-                // The chunk's W1 tiles were issued in the previous slot 5 (below), in K-tile order and BEFORE anything issued
-                // in this chunk's slots: tile kt + 1 (read by the H-waves in the next slot) has landed once at most the tiles
-                // behind it (kt + 2 .. 4) and this chunk's own W2 / bias pieces (h1 accumulates them) are outstanding; W2 and
-                // the bias are read in slot 5, so slot 4 waits for everything.
-                h1 += h0;
-                FTP(1, 3 * kt + 2);  // DMA issued
-                wait_vmcnt_rt(kt == 4 ? 0 : 4 * (3 - kt > 0 ? 3 - kt : 0) + h1);
-                if (kt == 4) h1 = 0;
-                (void)h2;
-#else
-                if (ld_left > 0) {   // W1 K tile LEAD slots ahead of the one the H-waves read now
-                    issue_w1();
-                    h0 += 4;
-                }
-                FTP(1, 3 * kt + 2);  // DMA issued
-                wait_vmcnt_rt(h0 + (LEAD >= 3 ? h1 : 0) + (LEAD >= 4 && kt != 4 ? h2 : 0));
-                h2 = h1; h1 = h0;
-#endif
-            }
-#endif
             FTP(1, 15);
             slot_barrier();
             FTP(1, 16);
-#if FFN_W1_BULK
             // slot 5: every H-wave is past its last read of the ring (slot 4) — the five stages are free.  The next chunk's W1 K
             // tiles go out here, in front of this wave's phase-2 MFMAs: the issue time (the ~110 cycles a VMEM instruction costs
             // its wave, x 20) falls under the H-waves' GEGLU, where this wave otherwise idles ~2 000 cycles, instead of pacing
@@ -741,15 +492,12 @@ __global__ __launch_bounds__(512, 2) void ffn_kernel(const FfnArgs p) {
             if (bulk) {
 #pragma unroll
                 for (int i = 0; i < NKT; ++i) issue_w1();
-#if FFN_BIAS_INIT
                 // ... and the next chunk's bias (parity buffer last read at the start of chunk cc - 1's K phase): resident,
                 // like the W1 tiles, at the end of this iteration — the H-waves' accumulators start at it behind barrier A
                 const int cn = c + 1 == NCH ? 0 : c + 1;
-                if (lane < 8) glds16((const char*)p.b1 + cn * (2 * HC * 4) + wq * 128 + lane * 16,
+                if (lane < 8) glds16_asm((const char*)p.b1 + cn * (2 * HC * 4) + wq * 128 + lane * 16,
                                      smem + BIAS_OFF + ((cc + 1) & 1) * BIAS_BYTES + wq * 128);
-#endif
             }
-#endif
             if (cc >= 1) {
                 // ---- phase 2 of chunk c2: Y += H . W2c^T  (H of the previous iteration, parity (cc - 1) & 1)
                 const char* hb = smem + H_OFF + ((cc - 1) & 1) * H_BYTES + (wq * 32 + frow) * 128;
@@ -770,17 +518,13 @@ __global__ __launch_bounds__(512, 2) void ffn_kernel(const FfnArgs p) {
                 // NO s_setprio here: with this wave at priority 1 the H-wave of the SIMD — evaluating the GEGLU on the VALU at
                 // the same time — is starved (its 1.6 k cycles of VALU work ran only AFTER these 80 MFMAs: 4.3 k cycles for the
                 // slot, tools/ffn_trace.py); at equal priority the older H-wave keeps its issue slots and the MFMAs, one issue
-                // per 16 cycles, take the rest
-                __builtin_amdgcn_s_setprio(FFN_P2_PRIO);
+                // per 16 cycles, take the rest (s_setprio 0: the priority this wave has anyway)
+                __builtin_amdgcn_s_setprio(0);
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                 for (int j = 0; j < 40; ++j) {
-#if FFN_ABLATE == 2
-                    asm volatile("" ::"v"(wf[j & 7]), "v"(hf[0][j / 20]), "v"(hf[1][j / 20]));
-#else
                     accY[0][j % 20] = WIW_MFMA(wf[j & 7], hf[0][j / 20], accY[0][j % 20]);
                     accY[1][j % 20] = WIW_MFMA(wf[j & 7], hf[1][j / 20], accY[1][j % 20]);
-#endif
                     if (j + 8 < 40) wf[j & 7] = wread(j + 8);
                     __builtin_amdgcn_sched_barrier(0);
                 }
@@ -933,10 +677,8 @@ __global__ __launch_bounds__(512, 2) void ffn_kernel(const FfnArgs p) {
                     ++ti;
                 }
             }
-#if FFN_W1_BULK
             FTP(1, 18);
-            if (bulk) wait_vmcnt<FFN_FREE_K ? 0 : 4 * (NKT - 1)>();   // W1 tile 0 (FFN_FREE_K: every tile) of the next chunk has landed (younger: tiles 1 .. 4; an epilogue's stores make this stricter)
-#endif
+            if (bulk) wait_vmcnt<0>();   // every W1 tile (and the bias) of the next chunk has landed
             c = c + 1 == NCH ? 0 : c + 1;
         }
 #ifdef WIW_FFN_TRACE

@@ -39,11 +39,10 @@
 #include <type_traits>
 
 #include "common.h"
+#include "lds_dma.h"
 
 namespace {
 
-typedef const __attribute__((address_space(1))) void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x2_t __attribute__((ext_vector_type(2)));
 // LDS-DMA, 16 bytes per lane, in the SADDR form: wave-uniform 64-bit block address in SGPRs + one 32-bit lane offset — a piece
@@ -56,10 +55,6 @@ WIW_DEV void glds16s(uint64_t sb, unsigned voff, uint32_t lds) {    // both wave
                  : "=&s"(keep) : "v"(voff), "s"(sb), "s"(lds) : "memory");
 }
 WIW_DEV void glds16(const char* sbase, unsigned voff, char* l) {
-#ifdef FF_DMA_BUILTIN
-    __builtin_amdgcn_global_load_lds((gptr_t)(sbase + voff), (lptr_t)l, 16, 0, 0);
-    return;
-#endif
     const uint32_t lds = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(lptr_t)l);
     // (the builtin returns a SIGNED int: without the casts a low half with bit 31 set sign-extends over the high half)
     const uint64_t sb = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)((uintptr_t)sbase >> 32)) << 32) |
@@ -84,14 +79,7 @@ constexpr int W1_OFF = W2_BYTES, W1_SLOT = 2 * CH * C * 2;     // one W1 chunk: 
 constexpr int B1_OFF = W1_OFF + 2 * W1_SLOT, B1_BYTES = 2 * HID * 4;
 constexpr int SMEM = B1_OFF + B1_BYTES;                        // 133 120 of the 163 840 bytes of a CU
 
-#ifndef FF_ABLATE
-#define FF_ABLATE 0   // timing experiments only (results wrong): 1 no GEGLU VALU, 2 no weight DMA in the loop, 4 no LDS fragment reads, 8 no barriers
-#endif
-#if FF_ABLATE & 4
-#define FF_DSR(dst, addr, off) asm volatile("" : "+v"(dst) : "v"(addr))
-#else
 #define FF_DSR(dst, addr, off) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "i"(off))
-#endif
 #define FF_WAIT(n) asm volatile("s_waitcnt lgkmcnt(" #n ")" ::: "memory")
 // a wait that also tells hipcc the named registers are defined HERE (cdna guide 5.7 form ii); only registers whose reads the
 // count covers may be named
@@ -235,7 +223,6 @@ __global__ __launch_bounds__(256, 1) void ffn32_kernel(const Ffn32Args p) {
         asm volatile("" : "+s"(w1n), "+s"(w2n), "+s"(w1dst));
         auto dma_piece = [&](auto s_tag) {
             constexpr int s = decltype(s_tag)::value;
-            if (FF_ABLATE & 2) return;
             if (s < 10 && next_cw >= 0) {
                 const int b = wave + 4 * s;
                 glds16s(w1n + (uint64_t)b * 1024, lane16, w1dst + (b % 5) * 8192 + (b / 5) * 1024);
@@ -261,11 +248,11 @@ __global__ __launch_bounds__(256, 1) void ffn32_kernel(const Ffn32Args p) {
                 else FF_WAIT2(0, fV[s % 3], fG[s % 3]);
                 if constexpr (s == 0) vgV[PAR] = FF_MFMA32(fV[0], xf[0], zero);
                 else vgV[PAR] = FF_MFMA32(fV[s % 3], xf[s], vgV[PAR]);
-                if constexpr (HASG && !(FF_ABLATE & 1)) geglu_gap(Qt{}, std::integral_constant<int, 2 * s>{});
+                if constexpr (HASG) geglu_gap(Qt{}, std::integral_constant<int, 2 * s>{});
                 FF_GAP
                 if constexpr (s == 0) vgG[PAR] = FF_MFMA32(fG[0], xf[0], zero);
                 else vgG[PAR] = FF_MFMA32(fG[s % 3], xf[s], vgG[PAR]);
-                if constexpr (HASG && !(FF_ABLATE & 1)) geglu_gap(Qt{}, std::integral_constant<int, 2 * s + 1>{});
+                if constexpr (HASG) geglu_gap(Qt{}, std::integral_constant<int, 2 * s + 1>{});
                 FF_GAP
             };
 #define FF_S20(f)                                                                                                                 \
@@ -281,7 +268,7 @@ __global__ __launch_bounds__(256, 1) void ffn32_kernel(const Ffn32Args p) {
             auto nslot = [&](auto s_tag) {
                 constexpr int s = decltype(s_tag)::value;
                 dma_piece(s_tag);
-                if constexpr (HASG && !(FF_ABLATE & 1)) {
+                if constexpr (HASG) {
                     geglu_gap(Qt{}, std::integral_constant<int, 2 * s>{});
                     geglu_gap(Qt{}, std::integral_constant<int, 2 * s + 1>{});
                 }
@@ -291,7 +278,7 @@ __global__ __launch_bounds__(256, 1) void ffn32_kernel(const Ffn32Args p) {
         // ---- an iteration that refilled the W2 tile: visible to everybody before phase 2 reads it
         if (refill) {
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            if (!(FF_ABLATE & 8)) __syncthreads();
+            __syncthreads();
         }
         // ---- S2
         {
@@ -323,12 +310,12 @@ __global__ __launch_bounds__(256, 1) void ffn32_kernel(const Ffn32Args p) {
                     else FF_WAIT1(4, fW[j % 4]);      // (everything older than the four reads issued behind the barrier has landed)
                     Y[ob] = FF_MFMA32(fW[j % 4], hb[ks].v, Y[ob]);
                 }
-                if constexpr (HASG && !(FF_ABLATE & 1)) geglu_gap(Qt{}, std::integral_constant<int, 40 + j>{});
+                if constexpr (HASG) geglu_gap(Qt{}, std::integral_constant<int, 40 + j>{});
                 FF_GAP
                 if constexpr (j == 17) {
                     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
                     if constexpr (HAS1) asm volatile("" : "+v"(bvq[0]), "+v"(bvq[1]), "+v"(bvq[2]), "+v"(bvq[3]), "+v"(bgq[0]), "+v"(bgq[1]), "+v"(bgq[2]), "+v"(bgq[3]));
-                    if (!(FF_ABLATE & 8)) __syncthreads();
+                    __syncthreads();
                     if (next_has1) {     // first fragment reads of the next iteration's phase 1
                         FF_DSR(fV[0], w1a[NS][0], 0);
                         FF_DSR(fG[0], w1a[NS][0], 4096);

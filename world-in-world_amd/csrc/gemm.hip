@@ -27,20 +27,12 @@
 //     All global loads of the epilogue are issued before the LDS transpose so their latency overlaps it.
 //   * tile order is XCD-aware: each of the 8 XCDs (private L2) gets a contiguous range of tiles.
 #include <stdlib.h>
-#ifndef WIW_DMA_BURST
-#define WIW_DMA_BURST 1   // 1: all DMA instructions of a K tile are issued in ONE slot (0: spread 2|2|2|1 over the four slots)
-#endif
-#ifndef WIW_ABLATE
-#define WIW_ABLATE 0
-#endif
 
 #include <mutex>
 #include <type_traits>
 
 #include "common.h"
-#ifndef WIW_GE_PK
-#define WIW_GE_PK 1   // GEGLU epilogue on packed pairs, breadth first (0: value by value, the round-2 form)
-#endif
+#include "lds_dma.h"
 
 // 256 x 320 tile variant (gemm_huge.hip)
 bool wiw_gemm_huge_ok(const WiwGemmArgs& a);
@@ -55,16 +47,6 @@ constexpr int STG_ROWB_G = 176;                   // GEGLU: 80 output cols + 16 
 constexpr int STG_WAVE = 32 * STG_ROWB_G;         // 5632 B per wave (plain: 16 rows x 336 B = 5376)
 static_assert(16 * STG_ROWB <= STG_WAVE, "");
 
-typedef const __attribute__((address_space(1))) void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
-
-WIW_DEV void glds16(const char* g, char* l) {
-#if WIW_ABLATE == 10   // no LDS-DMA at all (timing only: the MFMAs run on whatever the LDS holds)
-    asm volatile("" ::"v"(g), "s"(l));
-#else
-    __builtin_amdgcn_global_load_lds((gptr_t)g, (lptr_t)l, 16, 0, 0);
-#endif
-}
 // Sink for the epilogue stores / loads of lanes that own no valid output element: every epilogue VMEM
 // instruction is then executed by every wave unconditionally, which makes the number of stores queued behind the
 // prefetched LDS-DMA a compile-time constant (needed for the counted vmcnt waits below).
@@ -79,15 +61,6 @@ __device__ long long g_trace[2][4096];
 #else
 #define WIW_TP(idx) do { } while (0)
 #endif
-
-template <int N>
-WIW_DEV void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-
-WIW_DEV void wave_lds_sync() {   // order this wave's LDS writes before its following LDS reads (and vice versa)
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 
 // fp32-stream epilogue (F32E instantiations; WIW_EPI_OUT_F32 / _RES1_F32 / _RES2_F32 on aligned shapes): straight from the
@@ -158,25 +131,6 @@ WIW_DEV void wiw_epilogue_f32(const WiwGemmArgs& p, const f32x4 (&acc)[2][10], i
 // sums / sums of squares of its rows from the A fragments it feeds to the MFMAs anyway, and the fold is applied to the
 // fp32 accumulators in the fragment layout BEFORE the first 16-bit rounding.  The LayerNorm pass (one read + one write
 // of the activation) and the normalised tensor disappear.
-// One K tile forward in the implicit-GEMM K walk (see the cursor declaration in the kernel): tap-major, or channel-block
-// major under WIW_K_CMAJOR; the fused shortcut segment (tap 9, conv3x3 only) is walked last in both.
-struct WiwKCur { int tap, cc; };
-template <int MODE, int KT>
-WIW_DEV WiwKCur wiw_advance_k(WiwKCur c, const int Ctot, const bool cmajor) {   // by value: by-reference cursors end up in scratch
-    int ld_tap = c.tap, ld_cc = c.cc;
-    constexpr int NT = MODE == WIW_A_CONV_T3 ? 3 : 9;
-    if (MODE != WIW_A_DENSE && cmajor && !(MODE == WIW_A_CONV3X3 && ld_tap == 9)) {
-        if (++ld_tap == NT) {
-            ld_tap = 0;
-            ld_cc += KT;
-            if (MODE == WIW_A_CONV3X3 && ld_cc == Ctot) { ld_tap = 9; ld_cc = 0; }   // (only reached with a shortcut segment)
-        }
-    } else {
-        ld_cc += KT;
-        if (ld_cc == Ctot && !(MODE == WIW_A_CONV3X3 && ld_tap == 9)) { ld_cc = 0; ++ld_tap; }
-    }
-    return WiwKCur{ld_tap, ld_cc};
-}
 
 // F32E: the instantiation that serves the fp32 residual stream (ABI 11: WIW_EPI_OUT_F32 / _RES1_F32 / _RES2_F32 on aligned
 // shapes) — ONLY the vectorised fragment-layout epilogue is compiled into it, and it is compiled into no other instantiation
@@ -403,9 +357,8 @@ __global__ __launch_bounds__(NW * 64, 2) void gemm_kernel(const WiwGemmArgs p, c
         { const WiwKCur kc = wiw_advance_k<MODE, BK>(WiwKCur{ld_tap, ld_cc}, Ctot, cmajor); ld_tap = kc.tap; ld_cc = kc.cc; }
     };
 
-    // BIG: the 7 DMA instructions of a K tile are spread 2|2|2|1 over the four slots of the previous tile's
-    // iteration: an LDS-DMA instruction costs the issuing wave ~100 cycles, and a slot that carries all 7 is three
-    // times longer than the MFMA slot of the partner wave it is supposed to overlap.
+    // BIG: the 7 DMA instructions of a K tile in four parts (2|2|2|1); the main loop issues all four in ONE slot (see there;
+    // spread one part per slot, the earlier form, every slot paid the ~180-cycle first-DMA cost).
     auto issue_part = [&](int stage, auto part_tag) {
         constexpr int part = decltype(part_tag)::value;
         char* sA = smem + stage * STAGE_BYTES + wave * 4 * 1024;
@@ -433,9 +386,6 @@ __global__ __launch_bounds__(NW * 64, 2) void gemm_kernel(const WiwGemmArgs p, c
     // wave streams ds_read_b128 (and issues the DMA) while the other issues 20 MFMAs back to back.
     bf16x8 fa[2], fb[10];
     auto read_frags = [&](int stage, int kk) {
-#if WIW_ABLATE == 2
-        return;
-#endif
         const int sw = ((kk * 4 + fq) ^ (lane & 7)) << 4;
         const char* sA = smem + stage * STAGE_BYTES + (wave * 32 + frow) * 128 + sw;
         const char* sB = smem + stage * STAGE_BYTES + A_BYTES + frow * 128 + sw;
@@ -455,21 +405,13 @@ __global__ __launch_bounds__(NW * 64, 2) void gemm_kernel(const WiwGemmArgs p, c
         }
     };
     auto mma = [&]() {
-#if WIW_ABLATE == 1
-        asm volatile("" :: "v"(fa[0]), "v"(fb[0]));
-        return;
-#endif
-#if WIW_ABLATE != 3
         __builtin_amdgcn_s_setprio(1);
-#endif
 #pragma unroll
         for (int ni = 0; ni < 10; ++ni)
 #pragma unroll
             for (int mi = 0; mi < 2; ++mi)   // swapped operands: lane gets n = 16*ni + 4*fq + r, m = 16*mi + frow
                 acc[mi][ni] = WIW_MFMA(fb[ni], fa[mi], acc[mi][ni]);
-#if WIW_ABLATE != 3
         __builtin_amdgcn_s_setprio(0);
-#endif
         if (LNF) {   // row statistics from the A fragments just consumed (VALU, behind the MFMAs in flight)
 #pragma unroll
             for (int mi = 0; mi < 2; ++mi) {
@@ -483,18 +425,6 @@ __global__ __launch_bounds__(NW * 64, 2) void gemm_kernel(const WiwGemmArgs p, c
                 }
             }
         }
-    };
-    auto slot_barrier = [&]() {   // close a slot: this wave's LDS reads are retired, then rendezvous
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_sched_barrier(0);
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-        __builtin_amdgcn_sched_barrier(0);
-    };
-    auto slot_barrier_i = [&]() {   // intra-tile slot boundary
-#if WIW_ABLATE != 4
-        slot_barrier();
-#endif
     };
     const bool lag = wave >= NW / 2;   // wave-uniform: second wave group
 
@@ -568,7 +498,7 @@ __global__ __launch_bounds__(NW * 64, 2) void gemm_kernel(const WiwGemmArgs p, c
         };
         using I0 = std::integral_constant<int, 0>; using I1 = std::integral_constant<int, 1>;
         using I2 = std::integral_constant<int, 2>; using I3 = std::integral_constant<int, 3>;
-        using ILPT = std::integral_constant<int, LPT>; using I6 [[maybe_unused]] = std::integral_constant<int, LPT - 1>;
+        using ILPT = std::integral_constant<int, LPT>;
         wait_tile(0, ILPT{});
         if (NW == 8) {
             WIW_TP(0);
@@ -579,42 +509,25 @@ __global__ __launch_bounds__(NW * 64, 2) void gemm_kernel(const WiwGemmArgs p, c
                 const bool more = kt + D < nk;
                 int si = st_c + D;
                 si = si >= STAGES ? si - STAGES : si;
-#if WIW_DMA_BURST
                 // A slot that issues ANY LDS-DMA pays ~180 cycles once, every further instruction of the same slot ~25
                 // (tools/trace_probe.py): the 7 instructions of K tile kt+2 go out together here instead of 2|2|2|1
                 if (more) { issue_part(si, I0{}); issue_part(si, I1{}); issue_part(si, I2{}); issue_part(si, I3{}); }
-#else
-                if (more) issue_part(si, I0{});
-#endif
                 read_frags(st_c, 0);
                 WIW_TP(2 + 8 * kt);
-                slot_barrier_i();                                // 4kt+1
+                slot_barrier();                                  // 4kt+1
                 WIW_TP(3 + 8 * kt);
-#if !WIW_DMA_BURST
-                if (more) issue_part(si, I1{});
-#endif
                 mma();
                 WIW_TP(4 + 8 * kt);
-                slot_barrier_i();                                // 4kt+2
+                slot_barrier();                                  // 4kt+2
                 WIW_TP(5 + 8 * kt);
-#if !WIW_DMA_BURST
-                if (more) issue_part(si, I2{});
-#endif
                 read_frags(st_c, 1);
                 if (kt + 1 < nk) {
                     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#if WIW_DMA_BURST
                     wait_tile(kt + 1, ILPT{});                   // all 7 DMA instructions of tile kt+2 are younger
-#else
-                    wait_tile(kt + 1, I6{});                     // 6 of tile kt+2's 7 DMA instructions are younger
-#endif
                 }
                 WIW_TP(6 + 8 * kt);
-                slot_barrier_i();                                // 4kt+3
+                slot_barrier();                                  // 4kt+3
                 WIW_TP(7 + 8 * kt);
-#if !WIW_DMA_BURST
-                if (more) issue_part(si, I3{});
-#endif
                 mma();
                 WIW_TP(8 + 8 * kt);
                 st_c = (st_c + 1 == STAGES) ? 0 : st_c + 1;
@@ -827,30 +740,15 @@ __global__ __launch_bounds__(NW * 64, 2) void gemm_kernel(const WiwGemmArgs p, c
                         }
                         ov = pack8(v);
                     }
-#if WIW_ABLATE == 5
-                    uint4* dst = dump;
-#elif WIW_ABLATE == 7   // same bytes, but every store instruction writes 1 KiB contiguous (wrong layout: timing only)
-                    const int64_t lin = ((((int64_t)t * NW + wave) * 12 + (mi * 6 + k)) * 1024 + lane * 16) %
-                                        ((int64_t)p.M * p.ldo * 2 - 1024);
-                    uint4* dst = (uint4*)((char*)p.out + (lin & ~15ll));
-#else
                     uint4* dst = ok ? (uint4*)((uint16_t*)p.out + (int64_t)m * p.ldo + ncol) : dump;
-#endif
-#if WIW_ABLATE == 9
-                    *dst = ov;
-#else
                     // streaming (nt) store: the output tile is never re-read by this kernel, and a plain store
                     // allocates it in the XCD's 4 MiB L2 where it evicts the A / W panels the super-tile schedule
                     // keeps there (measured -17...-26 % on the K <= 1280 projections at L0)
                     __builtin_nontemporal_store(ov.x, &dst->x); __builtin_nontemporal_store(ov.y, &dst->y);
                     __builtin_nontemporal_store(ov.z, &dst->z); __builtin_nontemporal_store(ov.w, &dst->w);
-#endif
                 }
                 wave_lds_sync();
             };
-#if WIW_ABLATE == 6
-            if (p.M < 0) {
-#endif
             if constexpr (GE) {
                 // GEGLU: the output tile of a wave is 32 rows x 80 columns = 320 sixteen-byte chunks = EXACTLY five
                 // 64-lane sweeps (the 16-row passes above would take 2 x 3 sweeps of 6 rows and write two rows twice per
@@ -860,7 +758,6 @@ __global__ __launch_bounds__(NW * 64, 2) void gemm_kernel(const WiwGemmArgs p, c
 #pragma unroll
                 for (int mi = 0; mi < 2; ++mi) {
                     char* wrow = stg + (mi * 16 + frow) * STG_ROWB_G + fq * 8;
-#if WIW_GE_PK
                     // the 20 gates of these 16 rows as ten packed pairs, breadth first (gelu_erf_pk in common.h)
                     wiw_f32x2 gg[10];
 #pragma unroll
@@ -882,25 +779,6 @@ __global__ __launch_bounds__(NW * 64, 2) void gemm_kernel(const WiwGemmArgs p, c
                         pk.y = pack2bf(v[2] * gg[2 * ni + 1].x, v[3] * gg[2 * ni + 1].y);
                         *(uint2*)(wrow + ni * 32) = pk;
                     }
-#else
-#pragma unroll
-                    for (int ni = 0; ni < 5; ++ni) {
-                        f32x4 v = acc[mi][ni], g = acc[mi][ni + 5];
-                        if (LNF) {          // t carries the bias
-                            ln_fold4(v, ni, mi);
-                            ln_fold4(g, ni + 5, mi);
-                        } else if (p.bias) {
-                            v[0] += bvf[ni].x; v[1] += bvf[ni].y; v[2] += bvf[ni].z; v[3] += bvf[ni].w;
-                            g[0] += bvf[ni + 5].x; g[1] += bvf[ni + 5].y; g[2] += bvf[ni + 5].z; g[3] += bvf[ni + 5].w;
-                        }
-                        const wiw_f32x2 h01 = {v[0] * gelu_erf_f(g[0]), v[1] * gelu_erf_f(g[1])};
-                        const wiw_f32x2 h23 = {v[2] * gelu_erf_f(g[2]), v[3] * gelu_erf_f(g[3])};
-                        uint2 pk;
-                        pk.x = pack2bf(h01.x, h01.y);
-                        pk.y = pack2bf(h23.x, h23.y);
-                        *(uint2*)(wrow + ni * 32) = pk;
-                    }
-#endif
                 }
                 wave_lds_sync();
 #pragma unroll
@@ -922,14 +800,6 @@ __global__ __launch_bounds__(NW * 64, 2) void gemm_kernel(const WiwGemmArgs p, c
                 half_pass(std::integral_constant<bool, GE>{}, std::integral_constant<int, 1>{});
                 if (fast_st) pending_stores = 2 * ITEMS_P;
             }
-#if WIW_ABLATE == 6
-            } else {
-#pragma unroll
-                for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-                    for (int ni = 0; ni < 10; ++ni) asm volatile("" ::"v"(acc[mi][ni]));
-            }
-#endif
         } else {
             // direct path (fp32 output, SiLU, unaligned N / strides): element-wise from the fragment layout.
             // Every index into acc[][] is a compile-time constant (guards instead of break / continue).

@@ -16,7 +16,9 @@
 // Schedule per K tile (8 slots, a raw s_barrier between slots; waves 4..7 run one slot behind waves 0..3 so that on
 // every SIMD one wave reads LDS / issues DMA while its partner issues 20 MFMAs back to back):
 //     R(k0: A, W[0:5]) | M | R(k0: W[5:10]) | M | R(k1: A, W[0:5]) | M | R(k1: W[5:10]), confirm next tile | M
-// DMA of K tile kt+1 (9 instructions per wave) is issued 2|2|2|2|1 in slots 0..4 of tile kt.
+// DMA of K tile kt+1 (9 instructions per wave) is issued 2|2|2|2|1 in slots 0..4 of tile kt (all nine in ONE slot, which
+// won on the 256x160 tile and the temporal block, was 2-5 % slower on this tile).
+// This eight-slot loop serves the HALO_ == 2 instantiation only; every other instantiation runs the free-running PIPE loop.
 //
 // Instantiations (template <MODE, GE, SK, HALO_, F32E>): GE = GEGLU epilogue (dense), SK = split-K pass 1 (raw fp32 slabs),
 // HALO_ = 1 / 2: the 3x3 convolutions (stride 1, and behind a nearest x2 upsample) with a halo-staged A operand, 2 = plus the
@@ -24,15 +26,6 @@
 // fragment-layout epilogue of the fp32 residual stream.  Each is its own instantiation because this kernel lives at the
 // 256-VGPR limit: a feature compiled into the common one costs every launch registers or scratch.
 #include <stdlib.h>
-#ifndef WIW_DMA_BURST
-#define WIW_DMA_BURST 0   // 1: all DMA instructions of a K tile in ONE slot; 0: spread over five slots (measured: burst -2...-5 % on this tile, +2...+4 % on the 256x160 tile and the temporal block)
-#endif
-#ifndef WIW_ABLATE
-#define WIW_ABLATE 0
-#endif
-#ifndef WIW_HUGE_PIPE
-#define WIW_HUGE_PIPE 2   // 1: the free-running K loop of round 5 for every instantiation without a halo-staged A operand (below: PIPE); 2: also the halo-staged 3x3 convolutions
-#endif
 #if WIW_F16
 #define WIW_MFMA_ASM "v_mfma_f32_16x16x32_f16"
 #else
@@ -43,12 +36,7 @@
 #include <type_traits>
 
 #include "common.h"
-#ifndef WIW_GE_PK
-#define WIW_GE_PK 1   // 1: GEGLU epilogue on packed pairs, breadth first (gelu_erf_pk).  Round 3 measured it 3 % SLOWER here with the
-                      // A&S 7.1.26 erf (14 VALU: K = 640 595 vs 577 us, profiles/r06a_geglu_epilogue_ab.txt); with round 5's fitted
-                      // sigmoid form (10 VALU, 13 issues per PAIR packed) it is FASTER: M = 64 512, K = 640: 470-476 -> 455-462 us,
-                      // M = 16 128, K = 1280: 348-351 -> 344 us (profiles/r20l_geglu_epilogue_pk_ab.txt), bit-identical results; 0 = A/B
-#endif
+#include "lds_dma.h"
 
 namespace {
 
@@ -74,46 +62,13 @@ constexpr int HALO_BUF = 36864;                  // 4 x 144 pixels (Wd = 128) / 
 constexpr int HALO_SMEM = 2 * HB_BYTES + 2 * HALO_BUF;
 static_assert(4 * HSTG_WAVE <= HB_BYTES && 4 * HSTG_WAVE <= HALO_BUF, "HALO epilogue staging: 4 waves per free region");
 
-typedef const __attribute__((address_space(1))) void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
-
-WIW_DEV void glds16(const char* g, char* l) { __builtin_amdgcn_global_load_lds((gptr_t)g, (lptr_t)l, 16, 0, 0); }
-
 __device__ uint4 g_dump_h[512 * 64];   // sink of the unconditional epilogue stores (see gemm.hip)
-
-template <int N>
-WIW_DEV void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-
-WIW_DEV void wave_lds_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 template <int V> using IC = std::integral_constant<int, V>;
 
 // SK: split-K instantiation (raw fp32 slabs, no staged epilogue).  A separate template parameter because this kernel
 // lives at the 256-VGPR limit: with the split path compiled into the common instantiation its spills doubled
 // (80 -> 163 VGPRs) and every K >= 640 launch lost ~15 %.
-// One K tile forward in the implicit-GEMM K walk (see the cursor declaration in the kernel): tap-major, or channel-block
-// major under WIW_K_CMAJOR; the fused shortcut segment (tap 9, conv3x3 only) is walked last in both.
-struct WiwKCur { int tap, cc; };
-template <int MODE, int KT>
-WIW_DEV WiwKCur wiw_advance_k(WiwKCur c, const int Ctot, const bool cmajor) {   // by value: by-reference cursors end up in scratch
-    int ld_tap = c.tap, ld_cc = c.cc;
-    constexpr int NT = MODE == WIW_A_CONV_T3 ? 3 : 9;
-    if (MODE != WIW_A_DENSE && cmajor && !(MODE == WIW_A_CONV3X3 && ld_tap == 9)) {
-        if (++ld_tap == NT) {
-            ld_tap = 0;
-            ld_cc += KT;
-            if (MODE == WIW_A_CONV3X3 && ld_cc == Ctot) { ld_tap = 9; ld_cc = 0; }   // (only reached with a shortcut segment)
-        }
-    } else {
-        ld_cc += KT;
-        if (ld_cc == Ctot && !(MODE == WIW_A_CONV3X3 && ld_tap == 9)) { ld_cc = 0; ++ld_tap; }
-    }
-    return WiwKCur{ld_tap, ld_cc};
-}
 
 // HALO_: 0 = per-tap A tiles; 1 = halo-staged A operand; 2 = halo-staged + the fused shortcut segment behind the taps (a
 // separate instantiation: the segment's per-row loader state costs the plain one 8 VGPRs and 36 bytes of scratch)
@@ -140,7 +95,7 @@ __global__ __launch_bounds__(512, 2) void gemm_huge_kernel(const WiwGemmArgs p, 
     // DMA of tile kt + 2 may start right behind it.
     // HALO (round 5, second step): the same loop with the A fragments read from the halo buffers at the tap's offset; the
     // instantiation with the fused shortcut segment (HALO_ == 2: three kinds of K tile) keeps the slots.
-    constexpr bool PIPE = WIW_HUGE_PIPE != 0 && HALO_ != 2 && (!HALO || WIW_HUGE_PIPE >= 2);
+    constexpr bool PIPE = HALO_ != 2;
     static_assert(!HALO || ((MODE == WIW_A_CONV3X3 || MODE == WIW_A_CONV3X3_UP) && !GE && !SK) , "the halo-staged A operand is a plain 3x3 convolution");
     static_assert(!HSEG || MODE == WIW_A_CONV3X3, "the shortcut segment belongs to the stride-1 convolution");
     // UPH: nearest x2 upsample + 3x3 (WIW_A_CONV3X3_UP).  The staged image is the LOW-resolution input: tap (dy, dx) of output
@@ -338,14 +293,8 @@ __global__ __launch_bounds__(512, 2) void gemm_huge_kernel(const WiwGemmArgs p, 
                 }
             }
         } else if constexpr (part < 2) {
-#if WIW_ABLATE == 30   // timing experiment only (wrong results): the A tile of a 3x3 convolution is fetched for the centre tap
-                       // alone = the LDS-DMA instruction count of a halo-staged A operand (1 of 9 A tiles per channel block)
-            if (MODE != WIW_A_CONV3X3 || ld_tap == 4 || ld_tap == 9)
-#endif
-            {
             glds16(a_src(2 * part, ld_tap, ld_cc), sA + (2 * part) * 1024);
             glds16(a_src(2 * part + 1, ld_tap, ld_cc), sA + (2 * part + 1) * 1024);
-            }
         } else if constexpr (part < 4) {
             constexpr int i = 2 * (part - 2);
             glds16(w_row[i] + (int64_t)ld_kt * w_kstep, sB + i * 1024);
@@ -485,13 +434,6 @@ __global__ __launch_bounds__(512, 2) void gemm_huge_kernel(const WiwGemmArgs p, 
             for (int mi = 0; mi < 4; ++mi)   // swapped operands: lane gets n = 16*(5h+j) + 4*fq + r, m = 16*mi + frow
                 acc[mi][h * 5 + j] = WIW_MFMA(fb[j], fa[mi], acc[mi][h * 5 + j]);
         __builtin_amdgcn_s_setprio(0);
-    };
-    auto slot_barrier = [&]() {
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_sched_barrier(0);
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-        __builtin_amdgcn_sched_barrier(0);
     };
     const bool lag = wave >= 4;
 
@@ -731,6 +673,7 @@ __global__ __launch_bounds__(512, 2) void gemm_huge_kernel(const WiwGemmArgs p, 
 #undef HP_MMA
 #undef HP_WAIT
         } else {
+        // the eight-slot loop of the file header: the HALO_ == 2 instantiation only
         if (lag) slot_barrier();
         // one K tile.  cseg / fseg (HALO_ == 2 only): this tile / the tile fetched during it belongs to the shortcut segment —
         // compile-time, and the three kinds of tile run in three loops below: with run-time tests in ONE loop hipcc peeled
@@ -745,34 +688,20 @@ __global__ __launch_bounds__(512, 2) void gemm_huge_kernel(const WiwGemmArgs p, 
             // argument as for the ring stage below) — and is confirmed with this tile's vmcnt(0), long before its first use
             const bool hdo = HALO && !cseg && h_next < h_nblk && kt == h_tile;
             slot_barrier();                                    // 8kt
-#if WIW_DMA_BURST
-            // a slot that issues ANY LDS-DMA pays ~180 cycles once, further instructions ~25 each (tools/trace_probe.py)
-            if (more) issue_all(si);
-            if (HALO && hdo) issue_halo_all(m0, y0, h_next);
-#else
             issue_slot(si, IC<0>{}, IC<fseg>{}, more, hdo, m0, y0);
-#endif
             read_a(st_c, 0, kt, IC<cseg>{});
             read_b(st_c, 0, IC<0>{});
             slot_barrier();                                    // +1
-#if !WIW_DMA_BURST
             issue_slot(si, IC<1>{}, IC<fseg>{}, more, hdo, m0, y0);
-#endif
             mma(IC<0>{});
             slot_barrier();                                    // +2
-#if !WIW_DMA_BURST
             issue_slot(si, IC<2>{}, IC<fseg>{}, more, hdo, m0, y0);
-#endif
             read_b(st_c, 0, IC<1>{});
             slot_barrier();                                    // +3
-#if !WIW_DMA_BURST
             issue_slot(si, IC<3>{}, IC<fseg>{}, more, hdo, m0, y0);
-#endif
             mma(IC<1>{});
             slot_barrier();                                    // +4
-#if !WIW_DMA_BURST
             issue_slot(si, IC<4>{}, IC<fseg>{}, more, hdo, m0, y0);
-#endif
             read_a(st_c, 1, kt, IC<cseg>{});
             read_b(st_c, 1, IC<0>{});
             slot_barrier();                                    // +5
@@ -1015,17 +944,9 @@ __global__ __launch_bounds__(512, 2) void gemm_huge_kernel(const WiwGemmArgs p, 
                         }
                         ov = pack8(v);
                     }
-#if WIW_ABLATE == 21
-                    uint4* dst = dump;
-#else
                     uint4* dst = ok ? (uint4*)((uint16_t*)p.out + (int64_t)m * p.ldo + ncol) : dump;
-#endif
-#if WIW_ABLATE == 20
-                    *dst = ov;
-#else
                     __builtin_nontemporal_store(ov.x, &dst->x); __builtin_nontemporal_store(ov.y, &dst->y);
                     __builtin_nontemporal_store(ov.z, &dst->z); __builtin_nontemporal_store(ov.w, &dst->w);
-#endif
                 }
                 wave_lds_sync();
             };
@@ -1037,9 +958,10 @@ __global__ __launch_bounds__(512, 2) void gemm_huge_kernel(const WiwGemmArgs p, 
 #pragma unroll
                     for (int m2 = 0; m2 < 2; ++m2) {
                         char* wrow = stg + (m2 * 16 + frow) * HSTG_ROWB_G + fq * 8;
-#if WIW_GE_PK
                         // the 20 gates of these 16 rows as two blocks of five packed pairs, breadth first (gelu_erf_pk in
-                        // common.h; ten pairs at once cost 55 more spilled registers next to the 160 accumulators)
+                        // common.h; ten pairs at once cost 55 more spilled registers next to the 160 accumulators).  Against
+                        // value by value with the fitted sigmoid form: M = 64 512, K = 640: 470-476 -> 455-462 us, M = 16 128,
+                        // K = 1280: 348-351 -> 344 us, bit-identical results (profiles/r20l_geglu_epilogue_pk_ab.txt)
                         wiw_f32x2 ga[5], gb[5];
 #pragma unroll
                         for (int ni = 0; ni < 5; ++ni) {
@@ -1059,20 +981,6 @@ __global__ __launch_bounds__(512, 2) void gemm_huge_kernel(const WiwGemmArgs p, 
                             pk.y = pack2bf(v[2] * gb[ni].x, v[3] * gb[ni].y);
                             *(uint2*)(wrow + ni * 32) = pk;
                         }
-#else
-#pragma unroll
-                        for (int ni = 0; ni < 5; ++ni) {
-                            f32x4 v = acc[hh * 2 + m2][ni], g = acc[hh * 2 + m2][ni + 5];
-                            if (p.bias) {
-                                v[0] += bvf[ni].x; v[1] += bvf[ni].y; v[2] += bvf[ni].z; v[3] += bvf[ni].w;
-                                g[0] += bvf[ni + 5].x; g[1] += bvf[ni + 5].y; g[2] += bvf[ni + 5].z; g[3] += bvf[ni + 5].w;
-                            }
-                            uint2 pk;
-                            pk.x = pack2bf(v[0] * gelu_erf_f(g[0]), v[1] * gelu_erf_f(g[1]));
-                            pk.y = pack2bf(v[2] * gelu_erf_f(g[2]), v[3] * gelu_erf_f(g[3]));
-                            *(uint2*)(wrow + ni * 32) = pk;
-                        }
-#endif
                     }
                     wave_lds_sync();
 #pragma unroll
@@ -1140,7 +1048,7 @@ bool wiw_gemm_huge_ok(const WiwGemmArgs& a) {
     const bool ge = (a.epilogue & WIW_EPI_GEGLU) != 0;
     const bool f32 = (a.epilogue & (WIW_EPI_OUT_F32 | WIW_EPI_RES1_F32 | WIW_EPI_RES2_F32)) != 0;   // F32E instantiations (plain only)
     if (a.epilogue & (WIW_EPI_SILU | WIW_EPI_GELU | WIW_EPI_QUICK_GELU)) return false;
-    if (f32 && (ge || a.splitk > 1 || getenv("WIW_GEMM_HUGE_NO_F32"))) return false;
+    if (f32 && (ge || a.splitk > 1)) return false;
     // partial last N tile (the VAE's 256 / 512-channel layers): only without GEGLU and when 320-wide tiles idle no more
     // MFMA columns than 160-wide ones would
     if (a.N % HN != 0 && (ge || ((a.N + HN - 1) / HN) * HN > ((a.N + 159) / 160) * 160)) return false;
@@ -1154,7 +1062,7 @@ bool wiw_gemm_huge_ok(const WiwGemmArgs& a) {
     // (K = 320 GEGLU -6 %).  Plain epilogues at K = 320 were +-2 % while this kernel spilled; spill-free (round 4) the
     // 320-wide tile reads the A panel once instead of twice: M = 258 048, N = 320 138.7 -> 125.6 us with a residual,
     // 102.3 -> 88.5 without, N = 960 284 -> 250 (profiles/r10a_tile_probe.txt, r10b_tile_probe.txt)
-    if (a.K < 640 && ge && !getenv("WIW_GEMM_HUGE_ANYK")) return false;
+    if (a.K < 640 && ge) return false;
     const int64_t tiles = (int64_t)((a.M + HM - 1) / HM) * ((a.N + HN - 1) / HN);
     if (tiles < 200) return false;
     // persistent grid of one block per CU: a tile count just above a multiple of the CU count leaves the last round mostly
@@ -1192,7 +1100,7 @@ extern "C" int wiw_conv_halo_ok(const WiwGemmArgs* args) { return args != nullpt
 
 int wiw_gemm_huge_launch(hipStream_t s, const WiwGemmArgs& a) {
     const bool ge = (a.epilogue & WIW_EPI_GEGLU) != 0;
-    const bool a1 = a.mode == WIW_A_DENSE && a.C2 == 0 && a.M % HM == 0 && !getenv("WIW_GEMM_NO_A1");   // the A1 loader variant
+    const bool a1 = a.mode == WIW_A_DENSE && a.C2 == 0 && a.M % HM == 0;   // the A1 loader variant
     if (a.epilogue & WIW_K_HALO32) {
         if (!wiw_conv_halo_shape_ok(a)) {
             wiw_set_error("gemm: WIW_K_HALO32 launch outside the halo kernel's geometry (wiw_conv_halo_ok)");

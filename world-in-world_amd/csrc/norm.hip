@@ -23,13 +23,7 @@ constexpr int GROUPS = 32;
 // amplifies last-bit differences; the reference's GroupNorm is deterministic.)
 // ---------------------------------------------------------------------------------------------
 constexpr int GN_MAXC = 4096;
-#ifndef WIW_GN_U
-#define WIW_GN_U 4
-#endif
-#ifndef WIW_GN_WAVES
-#define WIW_GN_WAVES 5                  // waves per SIMD the register allocation is held to (96 VGPRs, no scratch)
-#endif
-constexpr int GN_U = WIW_GN_U;          // loads in flight per thread of the statistics pass (A/B: tools/build_variant.py)
+constexpr int GN_U = 4;                 // loads in flight per thread of the statistics pass
 
 // 8 consecutive channels starting at element offset `off` of a 16-bit (F32IN = false: one 16-byte load, returned packed)
 // or fp32 (two 16-byte loads) tensor.  The fp32 form serves the fp32 residual stream (ABI 11).
@@ -119,7 +113,8 @@ WIW_DEV void gn_fetch4x4(const float4* p0, const float4* p1, const float4* p2, c
 }
 
 template <bool F32IN>
-__global__ __launch_bounds__(256, WIW_GN_WAVES) void gn_stats_kernel(const void* __restrict__ X1, int C1,
+// 5 waves per SIMD: what the register allocation is held to (96 VGPRs, no scratch)
+__global__ __launch_bounds__(256, 5) void gn_stats_kernel(const void* __restrict__ X1, int C1,
                                                         const void* __restrict__ X2, int C2, int rows_per_unit,
                                                         int rows_per_block, float* partials, unsigned* counters,
                                                         float* __restrict__ stats) {
@@ -499,12 +494,6 @@ __global__ __launch_bounds__(GN1_THREADS) void gn_onepass_kernel(const uint16_t*
 // LayerNorm: one wave per row, row held in registers (C <= 2048 -> <= 4 chunks of 8 per lane),
 // exact two-pass mean / variance with 64-lane butterfly reductions.
 // ---------------------------------------------------------------------------------------------
-#ifndef LN_R_MID
-#define LN_R_MID 2     // rows in flight per wave at 512 < C <= 1024 (A/B knob)
-#endif
-#ifndef LN_R_WIDE
-#define LN_R_WIDE 1    // ... at C > 1024
-#endif
 constexpr int LN_MAXCH = 4;
 constexpr int LN_RUN = 8;      // consecutive rows per wave
 
@@ -787,8 +776,8 @@ extern "C" int wiw_layernorm_bf16(void* stream, const void* X, int64_t rows, int
     hipLaunchKernelGGL((layernorm_kernel<NCH, R, false>), grid, dim3(256), 0, (hipStream_t)stream, X, rows, C,        \
                        gamma, beta, eps, addvec, addvec_ld, rows_per_vec, (uint16_t*)sum_out, (uint16_t*)out)
     if (C <= 512) WIW_LN_LAUNCH(1, 8);
-    else if (C <= 1024) WIW_LN_LAUNCH(2, LN_R_MID);
-    else WIW_LN_LAUNCH(4, LN_R_WIDE);
+    else if (C <= 1024) WIW_LN_LAUNCH(2, 2);    // rows in flight per wave at 512 < C <= 1024
+    else WIW_LN_LAUNCH(4, 1);                  // ... at C > 1024
 #undef WIW_LN_LAUNCH
     return wiw_check_launch("wiw_layernorm_bf16");
 }

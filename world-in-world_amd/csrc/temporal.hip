@@ -30,17 +30,8 @@
 #include <type_traits>
 
 #include "common.h"
+#include "lds_dma.h"
 
-
-#ifndef WIW_T_ABLATE
-#define WIW_T_ABLATE 0    // resident form, timing experiments only: 1 = no epilogue, 2 = no A loads, 4 = no LDS reads of W, 8 = no row statistics
-#endif
-#ifndef WIW_T_STAGGER
-#define WIW_T_STAGGER 1   // resident form: waves 4..7 start half an item late (0: all waves in lock-step, A/B)
-#endif
-#ifndef WIW_T_MFMA_STATS
-#define WIW_T_MFMA_STATS 1   // 1: LayerNorm row statistics on the MATRIX pipe (round 4); 0: 16 v_dot2c per k-step (round 3, A/B)
-#endif
 // Row statistics on the matrix pipe: two extra MFMAs per site and k-step on operands the wave holds anyway,
 //     S = ONES . A^T  ->  every register of lane (frow = m, *) accumulates  sum_k x[m][k]          (ONES: a constant fragment)
 //     G = A . A^T     ->  lane (frow = m, fq = m >> 2), register m & 3 accumulates  sum_k x[m][k]^2  (the diagonal)
@@ -51,15 +42,9 @@
 // with the loads of those lanes masked out through EXEC so that their registers kept the ones: hipcc re-shuffles such
 // loop-carried "+v" registers with v_mov WHILE the asm loads are in flight — stale copies and loads landing in re-assigned
 // registers, a memory fault on the GPU.  tools/experiments/temporal_ones_row.txt.)
-#ifndef WIW_T_RES_S1_MFMA
-#define WIW_T_RES_S1_MFMA 0   // resident form (256-register limit): 1 = also the plain row sums S on the matrix pipe (the ones
-                              // fragment + its accumulators cost 12 registers: 32 bytes of scratch per lane, reloaded every K
-                              // tile); 0 = S stays on v_dot2c — 8 VALU instructions per k-step instead of 16 — and only G, the
-                              // sums of squares, moves to the matrix pipe
-#endif
-#ifndef WIW_T_EPI
-#define WIW_T_EPI 1       // 1: LayerNorm fold / output scaling of the epilogue on packed fp32 pairs (0: scalar FMAs, round 2)
-#endif
+// The resident form (256-register limit) moves only G, the sums of squares, to the matrix pipe: the ones fragment and the
+// accumulators of S cost 12 registers = 32 bytes of scratch per lane, reloaded every K tile, so S stays on v_dot2c there
+// (8 VALU instructions per k-step instead of 16).
 
 namespace {
 
@@ -72,8 +57,6 @@ constexpr int SCR_BYTES = 2048;                   // per-item fold vectors: s[19
 constexpr int STG_ROWB = 144;                     // staged O row: 64 bf16 + 16 B skew
 constexpr float LOG2E = 1.4426950408889634f;
 
-typedef const __attribute__((address_space(1))) void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
 // LDS-DMA as inline asm, M0 (the LDS address) saved / restored inside the statement.  NOT the builtin: hipcc knows that the
 // builtin writes LDS and puts `s_waitcnt vmcnt(0)` in front of the next LDS read it cannot prove disjoint — the epilogue's
 // fold-vector reads waited ~1 000 cycles for the next item's prefetch that had just been issued (r06c trace).  Completion
@@ -87,15 +70,7 @@ WIW_DEV void glds16(const char* base, uint32_t ofs, uint32_t lds_addr) {
     asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
                  : "=&s"(keep) : "v"(ofs), "s"(base), "s"(lds) : "memory");
 }
-template <int N>
-WIW_DEV void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-WIW_DEV wiw_f32x2 pk_fma(wiw_f32x2 a, wiw_f32x2 b, wiw_f32x2 c) { return __builtin_elementwise_fma(a, b, c); }
-WIW_DEV void glds16p(const char* g, uint32_t lds_addr) {   // the same with a per-lane 64-bit source address
-    const uint32_t lds = __builtin_amdgcn_readfirstlane(lds_addr);
-    uint32_t keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(g), "s"(lds) : "memory");
-}
+// (glds16_asm of lds_dma.h is the same with a per-lane 64-bit source address)
 // wave-uniform runtime count -> immediate (counts of this kernel are <= 1 + 2*3 + 4 + 4 + 3 = 18; more is clamped = stricter)
 WIW_DEV void wait_vmcnt_rt(int n) {
     switch (n < 18 ? n : 18) {
@@ -106,11 +81,6 @@ WIW_DEV void wait_vmcnt_rt(int n) {
 #undef WIW_VM_CASE
         default: wait_vmcnt<0>(); break;
     }
-}
-WIW_DEV void wave_lds_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 // sink of the O stores of lanes without a valid row (the store count per wave stays a compile-time constant)
 __device__ uint4 t_dump[512 * 64];
@@ -159,17 +129,11 @@ WIW_DEV void attention_epilogue(f32x4 (&acc)[2][NF], const float (&sum1)[2], con
         for (int ni = 0; ni < 8; ++ni) {
             const float4 sv = *(const float4*)(fs + ni * 16 + fq * 4);
             const float4 tv = *(const float4*)(fs + W_ROWS + ni * 16 + fq * 4);
-#if WIW_T_EPI == 1   // the same fp32 FMAs as packed pairs (v_pk_fma_f32: half the VALU instructions; no MFMA is in flight here)
+            // fp32 FMAs on packed pairs (v_pk_fma_f32: half the VALU instructions of the scalar form; no MFMA is in flight here)
             const wiw_f32x2 rs2 = {rs, rs}, nrm2 = {nrm, nrm};
             const wiw_f32x2 lo = pk_fma(wiw_f32x2{acc[mi][ni][0], acc[mi][ni][1]}, rs2, pk_fma(nrm2, wiw_f32x2{sv.x, sv.y}, wiw_f32x2{tv.x, tv.y}));
             const wiw_f32x2 hi = pk_fma(wiw_f32x2{acc[mi][ni][2], acc[mi][ni][3]}, rs2, pk_fma(nrm2, wiw_f32x2{sv.z, sv.w}, wiw_f32x2{tv.z, tv.w}));
             acc[mi][ni] = f32x4{lo.x, lo.y, hi.x, hi.y};
-#else
-            acc[mi][ni][0] = __builtin_fmaf(acc[mi][ni][0], rs, __builtin_fmaf(nrm, sv.x, tv.x));
-            acc[mi][ni][1] = __builtin_fmaf(acc[mi][ni][1], rs, __builtin_fmaf(nrm, sv.y, tv.y));
-            acc[mi][ni][2] = __builtin_fmaf(acc[mi][ni][2], rs, __builtin_fmaf(nrm, sv.z, tv.z));
-            acc[mi][ni][3] = __builtin_fmaf(acc[mi][ni][3], rs, __builtin_fmaf(nrm, sv.w, tv.w));
-#endif
         }
         // S^T = K . Q^T over d = 64 (two k-steps), lane: query frow, keys 4*fq + r
         f32x4 st = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -213,32 +177,19 @@ WIW_DEV void attention_epilogue(f32x4 (&acc)[2][NF], const float (&sum1)[2], con
         for (int nbk = 0; nbk < 4; ++nbk) {
             const float svv = fs[128 + nbk * 16 + frow], tvv = fs[W_ROWS + 128 + nbk * 16 + frow];
             union { uint32_t u[4]; bf16x8 v; } vo;
-#if WIW_T_EPI == 1
             const wiw_f32x2 sv2 = {svv, svv}, tv2 = {tvv, tvv};
             const wiw_f32x2 v01 = pk_fma(wiw_f32x2{acc[mi][8 + nbk][0], acc[mi][8 + nbk][1]}, wiw_f32x2{rsv[0], rsv[1]},
                                          pk_fma(wiw_f32x2{nrv[0], nrv[1]}, sv2, tv2));
             const wiw_f32x2 v23 = pk_fma(wiw_f32x2{acc[mi][8 + nbk][2], acc[mi][8 + nbk][3]}, wiw_f32x2{rsv[2], rsv[3]},
                                          pk_fma(wiw_f32x2{nrv[2], nrv[3]}, sv2, tv2));
             vo.u[0] = pack2bf(v01.x, v01.y); vo.u[1] = pack2bf(v23.x, v23.y); vo.u[2] = 0u; vo.u[3] = 0u;
-#else
-            float vv[4];
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-                vv[r] = __builtin_fmaf(acc[mi][8 + nbk][r], rsv[r], __builtin_fmaf(nrv[r], svv, tvv));
-            vo.u[0] = pack2bf(vv[0], vv[1]); vo.u[1] = pack2bf(vv[2], vv[3]); vo.u[2] = 0u; vo.u[3] = 0u;
-#endif
             f32x4 ot = f32x4{0.f, 0.f, 0.f, 0.f};
             ot = WIW_MFMA(vo.v, po.v, ot);
             uint2 pk;
-#if WIW_T_EPI == 1
             const wiw_f32x2 inv2 = {inv, inv};
             const wiw_f32x2 o01 = wiw_f32x2{ot[0], ot[1]} * inv2, o23 = wiw_f32x2{ot[2], ot[3]} * inv2;
             pk.x = pack2bf(o01.x, o01.y);
             pk.y = pack2bf(o23.x, o23.y);
-#else
-            pk.x = pack2bf(ot[0] * inv, ot[1] * inv);
-            pk.y = pack2bf(ot[2] * inv, ot[3] * inv);
-#endif
             if (frow < TP) *(uint2*)(wrow + nbk * 32) = pk;
         }
     }
@@ -267,7 +218,7 @@ WIW_DEV void attention_epilogue(f32x4 (&acc)[2][NF], const float (&sum1)[2], con
     wave_lds_sync();
 }
 
-// Row moments out of the Gram accumulators (WIW_T_MFMA_STATS): per-lane PARTIALS in the form attention_epilogue reduces (it
+// Row moments out of the Gram accumulators: per-lane PARTIALS in the form attention_epilogue reduces (it
 // sums over the four fq lanes of a row) — the lane that holds the moment contributes it, the others zero.
 WIW_DEV void stats_from_gram(const f32x4 (&s1)[2], const f32x4 (&g)[2], float (&sum1)[2], float (&sum2)[2], int lane) {
     asm volatile("" : "+v"(lane));
@@ -376,13 +327,13 @@ __global__ __launch_bounds__(NW * 64, 2) void temporal_block_kernel(const Tempor
         char* sA = smem + stage * STAGE_BYTES + wave * A_FULL * 1024;
         char* sW = smem + stage * STAGE_BYTES + A_BYTES + wave * W_FULL * 1024;
 #pragma unroll
-        for (int i = 0; i < A_FULL; ++i) glds16p(a_src(i), LDSA(sA + i * 1024));
+        for (int i = 0; i < A_FULL; ++i) glds16_asm(a_src(i), LDSA(sA + i * 1024));
         if (A_HALF) {
             char* sH = smem + stage * STAGE_BYTES + A_FULL * NW * 1024 + wave * 512;
-            if (lane < 32) glds16p(a_src(A_FULL), LDSA(sH));
+            if (lane < 32) glds16_asm(a_src(A_FULL), LDSA(sH));
         }
 #pragma unroll
-        for (int i = 0; i < W_FULL; ++i) glds16p(w_src(i), LDSA(sW + i * 1024));
+        for (int i = 0; i < W_FULL; ++i) glds16_asm(w_src(i), LDSA(sW + i * 1024));
         ++ld_kt;
     };
     // the same instructions spread over the four slots of the previous K tile: (A..) | (A.. + half) | (W0 W1) | (W2)
@@ -393,19 +344,19 @@ __global__ __launch_bounds__(NW * 64, 2) void temporal_block_kernel(const Tempor
         constexpr int A0 = (A_FULL + 1) / 2;   // full A instructions in part 0
         if (part == 0) {
 #pragma unroll
-            for (int i = 0; i < A0; ++i) glds16p(a_src(i), LDSA(sA + i * 1024));
+            for (int i = 0; i < A0; ++i) glds16_asm(a_src(i), LDSA(sA + i * 1024));
         } else if (part == 1) {
 #pragma unroll
-            for (int i = A0; i < A_FULL; ++i) glds16p(a_src(i), LDSA(sA + i * 1024));
+            for (int i = A0; i < A_FULL; ++i) glds16_asm(a_src(i), LDSA(sA + i * 1024));
             if (A_HALF) {
                 char* sH = smem + stage * STAGE_BYTES + A_FULL * NW * 1024 + wave * 512;
-                if (lane < 32) glds16p(a_src(A_FULL), LDSA(sH));
+                if (lane < 32) glds16_asm(a_src(A_FULL), LDSA(sH));
             }
         } else if (part == 2) {
-            glds16p(w_src(0), LDSA(sW));
-            glds16p(w_src(1), LDSA(sW + 1024));
+            glds16_asm(w_src(0), LDSA(sW));
+            glds16_asm(w_src(1), LDSA(sW + 1024));
         } else {
-            glds16p(w_src(2), LDSA(sW + 2048));
+            glds16_asm(w_src(2), LDSA(sW + 2048));
             ++ld_kt;
         }
     };
@@ -417,10 +368,8 @@ __global__ __launch_bounds__(NW * 64, 2) void temporal_block_kernel(const Tempor
         const int rho = wave * 2 * TP + mi * TP + (frow < TP ? frow : TP - 1);
         a_off[mi] = rho * 128 + ((fq ^ (rho & 7)) << 4);        // k-step 0; k-step 1 flips bit 2 of the chunk: ^ 64
     }
-#if WIW_T_MFMA_STATS
     f32x4 acc_s1[2], acc_s2[2];
     const bf16x8 ones = ones_fragment();
-#endif
     const int w_off = frow * 128 + ((fq ^ (frow & 7)) << 4);
 
     f32x4 acc[2][NF];
@@ -446,42 +395,12 @@ __global__ __launch_bounds__(NW * 64, 2) void temporal_block_kernel(const Tempor
 #pragma unroll
             for (int mi = 0; mi < 2; ++mi)   // v: lane = column (d) frow, rows (frames) 4*fq + r
                 acc[mi][ni] = WIW_MFMA(fa[mi], fb[ni], acc[mi][ni]);
-#if WIW_T_MFMA_STATS
 #pragma unroll
         for (int mi = 0; mi < 2; ++mi) {          // the two row moments (see the top of the file)
             acc_s1[mi] = WIW_MFMA(ones, fa[mi], acc_s1[mi]);
             acc_s2[mi] = WIW_MFMA(fa[mi], fa[mi], acc_s2[mi]);
         }
         __builtin_amdgcn_s_setprio(0);
-        return;
-#endif
-        // LayerNorm statistics from the A fragments just consumed: one v_dot2c per packed pair and moment (16 VALU
-        // instructions per k-step), each issued in the 16-cycle shadow of an MFMA.  (Round 2 unpacked to fp32 and ran
-        // 48 instructions AFTER the last MFMA: the wave issues in order, so they extended every MFMA slot by ~260 cycles.)
-#pragma unroll
-        for (int mi = 0; mi < 2; ++mi) {
-            union { bf16x8 v; uint32_t u[4]; } x;
-            x.v = fa[mi];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                sum1[mi] = dot2_acc(x.u[j], WIW_ONE16 * 0x10001u, sum1[mi]);
-                sum2[mi] = dot2_acc(x.u[j], x.u[j], sum2[mi]);
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);   // 1 MFMA
-            __builtin_amdgcn_sched_group_barrier(0x002, 1, 0);   // 1 VALU
-        }
-        __builtin_amdgcn_sched_group_barrier(0x008, 8, 0);
-        __builtin_amdgcn_s_setprio(0);
-    };
-    auto slot_barrier = [&]() {
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_sched_barrier(0);
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-        __builtin_amdgcn_sched_barrier(0);
     };
     const bool lag = wave >= NW / 2;
     const int nk = p.C / BK;
@@ -492,7 +411,7 @@ __global__ __launch_bounds__(NW * 64, 2) void temporal_block_kernel(const Tempor
     int st_c = 0;
     int parity = 0;                  // fold-vector scratch buffer of the current item
     int pending_stores = 0;
-    glds16p(Fb + f_ofs, LDSA(scratch + parity * SCR_BYTES + (wave & 1) * 1024));
+    glds16_asm(Fb + f_ofs, LDSA(scratch + parity * SCR_BYTES + (wave & 1) * 1024));
 #pragma unroll
     for (int j = 0; j < D; ++j)
         if (j < nk) issue_next(j);
@@ -508,10 +427,8 @@ __global__ __launch_bounds__(NW * 64, 2) void temporal_block_kernel(const Tempor
 #pragma unroll
         for (int mi = 0; mi < 2; ++mi) {
             sum1[mi] = 0.f; sum2[mi] = 0.f;
-#if WIW_T_MFMA_STATS
             acc_s1[mi] = f32x4{0.f, 0.f, 0.f, 0.f};
             acc_s2[mi] = f32x4{0.f, 0.f, 0.f, 0.f};
-#endif
 #pragma unroll
             for (int ni = 0; ni < NF; ++ni) acc[mi][ni] = f32x4{0.f, 0.f, 0.f, 0.f};
         }
@@ -562,7 +479,7 @@ __global__ __launch_bounds__(NW * 64, 2) void temporal_block_kernel(const Tempor
         if (item_next >= 0) {
             setup_loader(item_next);
             ld_kt = 0;
-            glds16p(Fb + f_ofs, LDSA(scratch + (parity ^ 1) * SCR_BYTES + (wave & 1) * 1024));
+            glds16_asm(Fb + f_ofs, LDSA(scratch + (parity ^ 1) * SCR_BYTES + (wave & 1) * 1024));
 #pragma unroll
             for (int j = 0; j < D; ++j) {
                 if (j < nk) {
@@ -575,9 +492,7 @@ __global__ __launch_bounds__(NW * 64, 2) void temporal_block_kernel(const Tempor
         int st_e = st_c + D;
         st_e = st_e >= STAGES ? st_e - STAGES : st_e;
 
-#if WIW_T_MFMA_STATS
         stats_from_gram(acc_s1, acc_s2, sum1, sum2, lane);
-#endif
         // ---- epilogue (per wave, no block barrier); O staging in the ring stage nobody reads or fills now
         attention_epilogue<TP>(acc, sum1, sum2, (const float*)(scratch + parity * SCR_BYTES),
                                smem + st_e * STAGE_BYTES + wave * STG_WAVE, p, b_cur, s0_cur, h_cur, wave, lane);
@@ -662,13 +577,7 @@ __global__ __launch_bounds__(NW * 64, 2) void temporal_block_resident_kernel(con
             asm volatile("global_load_dwordx4 %0, %1, %2 offset:64" : "=v"(dst[1][mi]) : "v"(vo), "s"(xb) : "memory");
         }
     };
-#if WIW_T_MFMA_STATS
     f32x4 acc_s2[2];
-#if WIW_T_RES_S1_MFMA
-    f32x4 acc_s1[2];
-    const bf16x8 ones = ones_fragment();
-#endif
-#endif
 
     const int w_off = frow * 128 + ((fq ^ (frow & 7)) << 4);
     f32x4 acc[2][NF];
@@ -683,12 +592,7 @@ __global__ __launch_bounds__(NW * 64, 2) void temporal_block_resident_kernel(con
         const int sw = w_off ^ ((step & 1) << 6);
 #pragma unroll
         for (int ni = hf * 6; ni < hf * 6 + 6; ++ni) {
-#if WIW_T_ABLATE & 4
-            if (step == 0) fb[ni] = *(const bf16x8*)(sW + ni * 2048 + sw);
-            asm volatile("" : "+v"(fb[ni]));
-#else
             fb[ni] = *(const bf16x8*)(sW + ni * 2048 + sw);
-#endif
         }
     };
     // 12 MFMAs of one half + the LayerNorm statistics of site hf (8 v_dot2c) in their shadow
@@ -703,11 +607,7 @@ __global__ __launch_bounds__(NW * 64, 2) void temporal_block_resident_kernel(con
                 else acc[mi][ni] = WIW_MFMA(a[mi], fb[ni], acc[mi][ni]);          // v
             }
         }
-#if WIW_T_MFMA_STATS && !(WIW_T_ABLATE & 8)
         acc_s2[hf] = WIW_MFMA(a[hf], a[hf], acc_s2[hf]);   // row sums of squares of site hf: the diagonal of A . A^T
-#if WIW_T_RES_S1_MFMA
-        acc_s1[hf] = WIW_MFMA(ones, a[hf], acc_s1[hf]);
-#else
         {
             union { bf16x8 v; uint32_t u[4]; } x;
             x.v = a[hf];
@@ -720,22 +620,6 @@ __global__ __launch_bounds__(NW * 64, 2) void temporal_block_resident_kernel(con
             }
             __builtin_amdgcn_sched_group_barrier(0x008, 5, 0);
         }
-#endif
-#elif !(WIW_T_ABLATE & 8)
-        union { bf16x8 v; uint32_t u[4]; } x;
-        x.v = a[hf];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            sum1[hf] = dot2_acc(x.u[j], WIW_ONE16 * 0x10001u, sum1[hf]);
-            sum2[hf] = dot2_acc(x.u[j], x.u[j], sum2[hf]);
-        }
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);   // 1 MFMA
-            __builtin_amdgcn_sched_group_barrier(0x002, 1, 0);   // 1 VALU
-        }
-        __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);
-#endif
         asm volatile("" : "+v"(sum1[hf]), "+v"(sum2[hf]));
         __builtin_amdgcn_s_setprio(0);
         __builtin_amdgcn_sched_barrier(0);
@@ -758,12 +642,7 @@ __global__ __launch_bounds__(NW * 64, 2) void temporal_block_resident_kernel(con
 #pragma unroll
         for (int mi = 0; mi < 2; ++mi) {
             sum1[mi] = 0.f; sum2[mi] = 0.f;
-#if WIW_T_MFMA_STATS
-#if WIW_T_RES_S1_MFMA
-            acc_s1[mi] = f32x4{0.f, 0.f, 0.f, 0.f};
-#endif
             acc_s2[mi] = f32x4{0.f, 0.f, 0.f, 0.f};
-#endif
 #pragma unroll
             for (int ni = 0; ni < NF; ++ni) acc[mi][ni] = f32x4{0.f, 0.f, 0.f, 0.f};
         }
@@ -773,12 +652,8 @@ __global__ __launch_bounds__(NW * 64, 2) void temporal_block_resident_kernel(con
             // the next A tile (of this item, or tile 0 of the next one) into the other buffer, then wait for THIS tile:
             // younger in the vmcnt queue are those loads and, at kt = 0, the previous item's O stores
             int younger = kt == 0 ? pending_stores : 0;
-#if WIW_T_ABLATE & 2   // timing only: no A loads after the first tile (stale operands)
-            if (false) load_a(fa[P ^ 1], a_ofs, kt + 1);
-#else
             if (kt + 1 < nk) { load_a(fa[P ^ 1], a_ofs, kt + 1); younger += A_LD; }
             else if (has_next) { load_a(fa[P ^ 1], a_nxt, 0); younger += A_LD; }
-#endif
             wait_vmcnt_rt(younger);
             asm volatile("" : "+v"(fa[P][0][0]), "+v"(fa[P][0][1]), "+v"(fa[P][1][0]), "+v"(fa[P][1][1]));
             RTP(2 + 2 * kt);
@@ -800,23 +675,9 @@ __global__ __launch_bounds__(NW * 64, 2) void temporal_block_resident_kernel(con
             if (kt + 1 < nk) ktile(std::integral_constant<int, START ^ 1>{}, kt + 1);
         }
         RTP(11);
-#if WIW_T_ABLATE & 1   // timing only: no attention epilogue (the accumulators are kept alive by an empty asm)
-#pragma unroll
-        for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-            for (int ni = 0; ni < NF; ++ni) asm volatile("" ::"v"(acc[mi][ni]));
-        asm volatile("" ::"v"(sum1[0]), "v"(sum1[1]), "v"(sum2[0]), "v"(sum2[1]));
-#else
         const int b_cur = mt / p.tiles_per_batch, s0_cur = (mt - b_cur * p.tiles_per_batch) * 16;
-#if WIW_T_MFMA_STATS
-#if WIW_T_RES_S1_MFMA
-        stats_from_gram(acc_s1, acc_s2, sum1, sum2, lane);
-#else
         sq_from_gram(acc_s2, sum2, lane);           // sum1 already holds the lanes' v_dot2c partials
-#endif
-#endif
         attention_epilogue<TP>(acc, sum1, sum2, fs, ostage + wave * STG_WAVE, p, b_cur, s0_cur, h, wave, lane);
-#endif
         RTP(12);
 #ifdef WIW_T_TRACE
         if (blockIdx.x == 0 && lane == 0 && r_ord == TR_ITEM)
@@ -824,11 +685,7 @@ __global__ __launch_bounds__(NW * 64, 2) void temporal_block_resident_kernel(con
                 g_rtrace[wave][i] = *(volatile __attribute__((address_space(3))) long long*)(lptr_t)(rt_base + (wave * 16 + i) * 8);
         ++r_ord;
 #endif
-#if WIW_T_ABLATE & 1
-        pending_stores = 0;
-#else
         pending_stores = NST;
-#endif
         mt = mt_next;
         a_ofs[0] = a_nxt[0]; a_ofs[1] = a_nxt[1];
         return has_next;
@@ -837,10 +694,8 @@ __global__ __launch_bounds__(NW * 64, 2) void temporal_block_resident_kernel(con
     // phase (each gets half the matrix pipe), then both in the VALU-bound epilogue (pipe idle).  Half an item of head start
     // for one of them makes the phases complementary, and complementary phases do not contend, so the offset persists.
     // (~512 cycles per s_sleep 8; half an item ~ (nk + 5) of them: ~5 000 cycles at C = 320, once per launch)
-#if WIW_T_STAGGER
     if (wave >= NW / 2)
         for (int i = 0; i < nk + 5; ++i) __builtin_amdgcn_s_sleep(8);
-#endif
     const bool flip = (nk & 1) != 0;
     while (true) {
         if (!item_body(I0{})) break;

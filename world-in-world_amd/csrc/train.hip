@@ -731,15 +731,9 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(const uint16_t* __res
 // ds_read_b64_tr_b16 (atb_tr_frag) — Q^T, K^T, dO^T never exist in memory.
 // Per step and wave: 32 MFMAs (dK/dV), 24 + 8 (dQ + its log-sum-exp pass), 16 KB of LDS reads.
 // ---------------------------------------------------------------------------------------------------------------------
-// Waves per SIMD the register allocator is held to (A/B knobs of the build: -DWIW_DKV_OCC= / -DWIW_DQ_OCC= lift them).  Both
+// Waves per SIMD the register allocator is held to (amdgpu_waves_per_eu on the two kernels below: dK/dV 3, dQ 4).  Both
 // kernels are bound by VALU issue beside their MFMAs (exp2, the dS products, packing), so a third / fourth resident wave
 // per SIMD is what fills the matrix pipe: dK/dV 164 VGPRs, dQ 124, no spills (profiles/r04b_attn_bwd_ab.txt).
-#ifndef WIW_DKV_OCC
-#define WIW_DKV_OCC __attribute__((amdgpu_waves_per_eu(3, 3)))
-#endif
-#ifndef WIW_DQ_OCC
-#define WIW_DQ_OCC __attribute__((amdgpu_waves_per_eu(4, 4)))
-#endif
 constexpr int ATB_ROW = 72;    // elements per LDS row of a [32 rows][64 d] tile (144 B: 16-byte reads of 16 rows spread over the banks)
 
 // Transposed MFMA operand straight from a ROW-MAJOR [32 rows][64 d] LDS tile with ds_read_b64_tr_b16: every lane hands in
@@ -757,7 +751,7 @@ __device__ __forceinline__ bf16x8 atb_tr_frag(const uint16_t* tile, int db, int 
 }
 
 template <int D>
-__global__ __launch_bounds__(256) WIW_DKV_OCC void attn_bwd_dkv_tiled_kernel(const uint16_t* __restrict__ QKV, int ld, int k_off, int v_off,
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) void attn_bwd_dkv_tiled_kernel(const uint16_t* __restrict__ QKV, int ld, int k_off, int v_off,
                                                                   const uint16_t* __restrict__ dO, int ldo,
                                                                   uint16_t* __restrict__ dQKV, int ldd, const float* __restrict__ LSE,
                                                                   const float* __restrict__ Dsum, int S, int heads, int k_blocks,
@@ -862,7 +856,7 @@ __global__ __launch_bounds__(256) WIW_DKV_OCC void attn_bwd_dkv_tiled_kernel(con
 }
 
 template <int D>
-__global__ __launch_bounds__(256) WIW_DQ_OCC void attn_bwd_dq_tiled_kernel(const uint16_t* __restrict__ QKV, int ld, int k_off, int v_off,
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) void attn_bwd_dq_tiled_kernel(const uint16_t* __restrict__ QKV, int ld, int k_off, int v_off,
                                                                  const uint16_t* __restrict__ O, const uint16_t* __restrict__ dO, int ldo,
                                                                  uint16_t* __restrict__ dQKV, int ldd, float* __restrict__ LSE,
                                                                  float* __restrict__ Dsum, int S, int heads, int q_blocks, float scale,

@@ -4,7 +4,12 @@ weight-gradient GEMM over orientation (dW vs dW^T) and split-K factors at the se
 
 `--max_grad_norm C` instead measures what global-norm gradient clipping costs: the whole `Trainer.step` (PH x PW x 14, default
 576 x 1024) without and with the threshold, in one process on one box, in alternating blocks (off, on, off, on), plus the
-norm kernels on their own (ms and GB/s over the trainer's own gradient tensors)."""
+norm kernels on their own (ms and GB/s over the trainer's own gradient tensors).
+
+`--manip448` measures the fine-tuning step of the served network on a 448 x 448 x 14 manipulation clip (56 x 56 latent: levels of
+3136, 784, 196 and 49 tokens, 10 action channels): forward / backward / whole `Trainer.step` ms, peak memory, the kernel-family
+rows `Hip._timed` keeps, the GEMMs by mode, and every attention call by sequence length — the padded form (`attn_small` + the
+one-wave backward at S = 196 and 49) and the one-wave backward at S = 784 next to the LDS-tiled S = 3136."""
 import argparse
 import collections
 import os
@@ -204,13 +209,99 @@ def clip_cost(max_grad_norm: float, steps: int = 5, dtype=torch.bfloat16):
                       "table_uploads_total": net.hip.sumsq_table_uploads}))
 
 
+def manip448_step(dtype=torch.bfloat16, steps: int = 5):
+    import json
+    import statistics
+
+    import numpy as np
+
+    from wiw_amd.pipeline import SCENE_BOUNDS, manip_action_ids
+    from wiw_amd.train_unet import Trainer, attn_level_plan
+
+    Tn, h, w = 14, 56, 56
+    cfg = UNetConfig(num_frames=Tn, action_input_channel=10, task_type="manipulation")
+    net = UNetTrain(cfg, random_state_dict_torch(cfg, 0, dev, torch.float32), dev, dtype=dtype)
+    hip = net.hip
+    gen = torch.Generator().manual_seed(100)
+    rs = np.random.RandomState(0)
+    poses = np.zeros((1, Tn, 8), np.float32)
+    poses[..., :3] = SCENE_BOUNDS[:3] + (SCENE_BOUNDS[3:] - SCENE_BOUNDS[:3]) * rs.uniform(0.1, 0.9, size=(1, Tn, 3))
+    poses[..., 3:7] = rs.standard_normal((1, Tn, 4))
+    poses[..., 7] = rs.choice([0.0, 1.0], size=(1, Tn))
+    lat, noise = torch.randn(1, Tn, 4, h, w, generator=gen) * 0.8, torch.randn(1, Tn, 4, h, w, generator=gen)
+    st = T.prepare_step(lat, noise, 1.3, torch.randn(1, 4, h, w, generator=gen), torch.randn(1, 1, 1024, generator=gen), 0.04,
+                        torch.from_numpy(manip_action_ids(poses)))
+    T.clear_wgrad_plans()
+    tr = Trainer(net, lr=1e-5, autotune=True)
+    for _ in range(2):                                   # warm-up: weight-gradient plans, allocator
+        tr.step(st)
+    torch.cuda.synchronize()
+    torch.cuda.reset_peak_memory_stats()
+
+    def wall(fn):
+        torch.cuda.synchronize(); t0 = time.perf_counter()
+        out = fn()
+        torch.cuda.synchronize()
+        return 1e3 * (time.perf_counter() - t0), out
+
+    fwd, bwd, whole = [], [], []
+    for _ in range(steps):
+        ms, pred = wall(lambda: net.forward(st.unet_input, st.timestep, st.ehs, st.added_time_ids, st.action_ids))
+        fwd.append(ms)
+        loss, dpred = T.TrainStep(hip).loss_and_grad(pred, st)
+        bwd.append(wall(lambda: net.backward(dpred.reshape(pred.shape), tr.loss_scale))[0])
+    for _ in range(steps):
+        whole.append(wall(lambda: tr.step(st))[0])
+    peak = torch.cuda.max_memory_allocated() / 2 ** 30
+    # one more step with events: families, GEMM modes, every attention call by sequence length
+    arecs = []
+
+    def awrap(name, key):
+        f = getattr(hip, name)
+
+        def g(*a, **k):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(); out = f(*a, **k); e1.record()
+            arecs.append((f"{name} {key(a, k)}", e0, e1))
+            return out
+        setattr(hip, name, g)
+    awrap("attn_spatial", lambda a, k: f"S={a[8]}" + (" +lse" if k.get("lse") is not None else ""))
+    awrap("attn_small", lambda a, k: f"S={a[8]} Sp={a[9]}")
+    awrap("attn_backward", lambda a, k: f"S={a[4]} Sp={k.get('Sp') or a[4]}" + (" given lse" if k.get("lse") is not None else ""))
+    hip.kernel_profile, hip.gemm_profile = [], []
+    ms_prof, _ = wall(lambda: tr.step(st))
+    fam = collections.defaultdict(lambda: [0, 0.0])
+    for e0, e1, family, _, _ in hip.kernel_profile:
+        fam[family][0] += 1; fam[family][1] += e0.elapsed_time(e1)
+    gm = collections.defaultdict(lambda: [0, 0.0])
+    for e0, e1, _, mode, _ in hip.gemm_profile:
+        gm[f"gemm mode {mode}"][0] += 1; gm[f"gemm mode {mode}"][1] += e0.elapsed_time(e1)
+    at = collections.defaultdict(lambda: [0, 0.0])
+    for key, e0, e1 in arecs:
+        at[key][0] += 1; at[key][1] += e0.elapsed_time(e1)
+    hip.kernel_profile = hip.gemm_profile = None
+    step_ms = statistics.median(whole)
+    rows = lambda d: {k: {"calls": n, "ms": round(ms, 3), "share_of_step": round(ms / step_ms, 4)}  # noqa: E731
+                      for k, (n, ms) in sorted(d.items(), key=lambda kv: -kv[1][1])}
+    print(json.dumps({"probe": "manip448_train_step", "size": f"448x448x{Tn}", "latent": [h, w], "dtype": str(dtype),
+                      "levels_S_Sp": attn_level_plan(h, w), "forward_ms": round(statistics.median(fwd), 2),
+                      "backward_ms": round(statistics.median(bwd), 2), "step_ms": round(step_ms, 2),
+                      "step_ms_all": [round(x, 1) for x in whole], "step_ms_with_events": round(ms_prof, 1),
+                      "peak_GiB": round(peak, 2), "loss_scale": tr.loss_scale, "attention_calls": rows(at),
+                      "kernel_families": rows(fam), "gemms": rows(gm), "wgrad_plans": len(T.wgrad_plans())}))
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--max_grad_norm", type=float, default=None, help="measure the cost of global-norm gradient clipping at this "
                     "threshold (the reference's DeepSpeed config uses 0.5) instead of the operator / sweep probes")
-    ap.add_argument("--steps", type=int, default=5, help="--max_grad_norm: timed steps per block")
+    ap.add_argument("--manip448", action="store_true", help="time the fine-tuning step on a 448 x 448 x 14 manipulation clip")
+    ap.add_argument("--steps", type=int, default=5, help="--max_grad_norm / --manip448: timed steps per block")
     ap.add_argument("--dtype", choices=["bf16", "fp16"], default="bf16")
     args = ap.parse_args()
+    if args.manip448:
+        manip448_step(torch.float16 if args.dtype == "fp16" else torch.bfloat16, args.steps)
+        sys.exit(0)
     if args.max_grad_norm is not None:
         clip_cost(args.max_grad_norm, args.steps, torch.float16 if args.dtype == "fp16" else torch.bfloat16)
         sys.exit(0)

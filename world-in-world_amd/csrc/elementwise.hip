@@ -131,7 +131,8 @@ inline int grid_for(int64_t total, int block) {
     return (int)g;
 }
 
-// Y[c][r] = X[r][c0 + c]  (16-bit), 64 x 64 tiles through LDS: 128-byte row segments on both sides.
+// Y[c][r] = X[r][c0 + c]  (16-bit), 64 x 64 tiles through LDS: 128-byte row segments on both sides.  Any row count: the
+// columns of Y from `rows` up to the next multiple of 8 are written as zeros.
 // Hands the attention kernel V^T from a V that one fused q|k|v projection wrote row-major, and the training step the
 // K-contiguous operands of its weight-gradient GEMMs.  A thread loads the same 8 columns of TWO consecutive rows and
 // writes 8 words (X[2p][c] | X[2p+1][c] << 16) into tile[c][p] — the 2 x 2 transposes happen in registers, so LDS sees
@@ -145,10 +146,10 @@ __global__ __launch_bounds__(256) void transpose_bf16_kernel(const uint16_t* __r
     {
         const int p = tid >> 3, ch = tid & 7;                     // row pair, 16-byte chunk
         uint4 a = uint4{0u, 0u, 0u, 0u}, b = a;
-        if (cb + ch * 8 < C && r0 + 2 * p < rows) {               // rows % 8 == 0: the pair is inside or outside together
+        if (cb + ch * 8 < C && r0 + 2 * p < rows) {
             const uint16_t* src = X + (r0 + 2 * p) * ldx + c0 + cb + ch * 8;
             a = *(const uint4*)src;
-            b = *(const uint4*)(src + ldx);
+            if (r0 + 2 * p + 1 < rows) b = *(const uint4*)(src + ldx);   // odd row count: the last pair's second row is a zero
         }
         const uint32_t au[4] = {a.x, a.y, a.z, a.w}, bu[4] = {b.x, b.y, b.z, b.w};
 #pragma unroll
@@ -172,8 +173,11 @@ __global__ __launch_bounds__(256) void transpose_bf16_kernel(const uint16_t* __r
 
 extern "C" int wiw_transpose_bf16(void* stream, const void* X, int64_t ldx, int c0, int64_t rows, int C, void* Y, int64_t ldy) {
     WIW_REQUIRE(X && Y, "transpose: null pointer");
-    WIW_REQUIRE(rows > 0 && C > 0 && rows % 8 == 0 && C % 8 == 0 && c0 % 8 == 0 && ldx % 8 == 0 && ldy % 8 == 0,
-                "transpose: rows, C, c0, ldx, ldy must be multiples of 8");
+    WIW_REQUIRE(rows > 0 && C > 0 && C % 8 == 0 && c0 % 8 == 0 && ldx % 8 == 0 && ldy % 8 == 0,
+                "transpose: C, c0, ldx, ldy must be multiples of 8");
+    // any row count (the conv weight gradients of a 7 x 7 level transpose 4 x 49 rows): Y is written in 8-column groups, so its
+    // columns rows .. 8 ceil(rows / 8) - 1 receive zeros and must exist
+    WIW_REQUIRE(rows % 8 == 0 || ldy >= (rows + 7) / 8 * 8, "transpose: ldy must cover rows rounded up to a multiple of 8");
     hipLaunchKernelGGL(transpose_bf16_kernel, dim3((unsigned)((rows + 63) / 64), (unsigned)((C + 63) / 64)), dim3(256), 0,
                        (hipStream_t)stream, (const uint16_t*)X, ldx, c0, rows, C, (uint16_t*)Y, ldy);
     return wiw_check_launch("wiw_transpose_bf16");

@@ -874,6 +874,31 @@ class Hip:
                  "wiw_attn_bwd_bf16")
         return dqkv
 
+    def attn_padded(self, qkv, seqs, S, heads, scale):
+        """Self-attention forward for ANY sequence length on the fused q|k|v layout: qkv [>= seqs*S, 3C] (C = heads*64), the
+        sequences contiguous -> (O [seqs*S, C], saved).  The rows are re-ordered to a row stride of Sp = 16 ceil(S / 16) (pad
+        rows zero: `row_map` T_TO_SEQ with one "site" per sequence), V^T is the transpose of the padded rows (its pad columns
+        are zeros, so a masked probability multiplies a finite value) and `attn_small` masks the keys >= S.  `saved` (the
+        padded operands and the padded output) is what `attn_padded_backward` reads."""
+        Cn, Sp = heads * 64, -(-S // 16) * 16
+        Ms = seqs * Sp
+        q_seq = self.row_map(qkv, self.ROW_T_TO_SEQ, Ms, 3 * Cn, T=S, Tp=Sp, S=1)
+        vt = torch.empty(Cn, Ms, dtype=self.dtype, device=self.device)
+        self.transpose(q_seq, 3 * Cn, 2 * Cn, Ms, Cn, vt, Ms)
+        o_seq = torch.empty(Ms, Cn, dtype=self.dtype, device=self.device)
+        self.attn_small(q_seq, 3 * Cn, Cn, vt, Ms, o_seq, Cn, seqs, S, Sp, heads, 64, scale)     # writes all Sp rows (pad: zeros)
+        O = self.row_map(o_seq, self.ROW_SEQ_TO_T, seqs * S, Cn, T=S, Tp=Sp, S=1)
+        return O, (q_seq, o_seq, seqs, S, Sp, heads, scale)
+
+    def attn_padded_backward(self, saved, dO):
+        """dO [seqs*S, C] -> d_qkv [seqs*S, 3C]: the one-wave-per-tile backward on the padded operands of `attn_padded`
+        (`attn_backward(..., Sp=Sp)`; its pad rows come out zero and are dropped on the way back)."""
+        q_seq, o_seq, seqs, S, Sp, heads, scale = saved
+        Cn = heads * 64
+        do_seq = self.row_map(dO, self.ROW_T_TO_SEQ, seqs * Sp, Cn, T=S, Tp=Sp, S=1)
+        dq_seq = self.attn_backward(q_seq, o_seq, do_seq, seqs, S, heads, scale, Sp=Sp)
+        return self.row_map(dq_seq, self.ROW_SEQ_TO_T, seqs * S, 3 * Cn, T=S, Tp=Sp, S=1)
+
     def gather_taps(self, X, M, Cn, H, Wd, T=1, temporal=False, stride=1):
         """im2col rows [M, taps*Cn] of X for the conv weight gradients (9 taps, or 3 temporal ones); M = OUTPUT rows,
         (H, Wd) = output geometry (stride 2: X is the (2H, 2Wd) input)."""

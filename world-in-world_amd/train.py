@@ -69,7 +69,7 @@ def prepare_step(latents: torch.Tensor, noise: torch.Tensor, sigma: float, cond_
 @torch.no_grad()
 def batch_from_pixels(front, pixel_values: torch.Tensor, past_obs: torch.Tensor, actions, *, scaling_factor: Optional[float] = None,
                       dropout_prob: Optional[float] = None, generator: Optional[torch.Generator] = None,
-                      draws: Optional[dict] = None) -> StepInputs:
+                      draws: Optional[dict] = None, action_input_channel: int = 10) -> StepInputs:
     """One training sample from PIXELS, as the reference's loop builds it (train_svd.py:846-931), on the HIP front end:
         latents      = vae.encode(frames).latent_dist.sample() * scaling_factor            (:86-95, :856)
         noise        = sample_latent_noise(actions, ...)                                    (:873; pipeline:750-786)
@@ -79,11 +79,14 @@ def batch_from_pixels(front, pixel_values: torch.Tensor, past_obs: torch.Tensor,
         ehs          = CLIP(resize_224(past_obs))   (norm_image + feature_extractor normalise + image_encoder, :893-894)
     then `prepare_step` (noisy latents, EDM input scaling, conditioning dropout, t = 0.25 ln sigma).
     front: `vae.HIPFrontend` (VAEHIP.encode_moments, CLIPVisionHIP).  pixel_values (1, T, 3, H, W) and past_obs (1, P, 3, H', W')
-    fp32 in [-1, 1]; actions (1, T) ints.  `draws` overrides the random draws (tests / replay): vae_eps (T, L, h, w), cond_eps
+    fp32 in [-1, 1]; actions (1, T) navigation ids, or — decided by the rank of the array, as `SVDDenoiser.denoise` — (1, T, 8)
+    manipulation rows [x, y, z, qx, qy, qz, qw, gripper]: `manip_action_ids` (10 channels; their positional form when the
+    network's `action_input_channel` is T + 9) and NO noise rotation (the reference's `sample_latent_noise(..., args.task_type)`
+    rotates the panorama for navigation only).  `draws` overrides the random draws (tests / replay): vae_eps (T, L, h, w), cond_eps
     (1, L, h, w), pixel_noise (1, 3, H, W), latent_noise (1, T, L, h, w), sigma, cond_sigma (floats), random_p ((1,))."""
     import numpy as np
 
-    from .pipeline import action_ids_idx_encode, rotate_latent_noise
+    from .pipeline import action_encode_positional, action_ids_idx_encode, manip_action_ids, rotate_latent_noise
 
     d = dict(draws or {})
     vae = front.vae
@@ -102,9 +105,19 @@ def batch_from_pixels(front, pixel_values: torch.Tensor, past_obs: torch.Tensor,
         mean, logvar = vae.encode_moments(x)
         return mean + torch.exp(0.5 * logvar) * randn(eps_name, tuple(mean.shape))
 
+    manip = np.asarray(actions).ndim == 3
+    if manip:
+        ids = manip_action_ids(np.asarray(actions).reshape(1, T, 8))
+        if action_input_channel == T + ids.shape[-1] - 1 and action_input_channel != ids.shape[-1]:
+            ids = action_encode_positional(ids)
+        if ids.shape[-1] != action_input_channel:
+            raise ValueError(f"manipulation action ids have {ids.shape[-1]} channels (or {T + 9} in their positional form), the "
+                             f"UNet embeds {action_input_channel} (action_input_channel: 10 or T + 9)")
     latents = (sample(px, "vae_eps") * sf)[None]                                             # (1, T, L, h, w)
-    acts = np.asarray(actions).reshape(1, T)
-    noise = rotate_latent_noise(randn("latent_noise", tuple(latents.shape)), acts)
+    noise = randn("latent_noise", tuple(latents.shape))
+    if not manip:
+        acts = np.asarray(actions).reshape(1, T)
+        noise = rotate_latent_noise(noise, acts)
     cond_sigma = float(d["cond_sigma"]) if "cond_sigma" in d else float(rand_log_normal([1], -3.0, 0.5, generator)[0])
     cond_px = px[0:1] + randn("pixel_noise", tuple(px[0:1].shape)) * cond_sigma
     cond_latents = sample(cond_px, "cond_eps")                                                # * sf / sf
@@ -113,7 +126,7 @@ def batch_from_pixels(front, pixel_values: torch.Tensor, past_obs: torch.Tensor,
     assert po.reshape(-1, *po.shape[-3:]).shape[0] == 1, "one past observation per sample (train_svd.sh; UNetTrain takes (1, 1, D))"
     e = front._embed(po.reshape(-1, *po.shape[-3:]), None)                                    # (1, 1, D) fp32
     ehs = e.reshape(1, 1, e.shape[-1])
-    action_ids = torch.from_numpy(action_ids_idx_encode(acts))
+    action_ids = torch.from_numpy(ids if manip else action_ids_idx_encode(acts))
     random_p = None
     if dropout_prob is not None:
         random_p = torch.as_tensor(d["random_p"]) if "random_p" in d else torch.rand(1, generator=generator)
@@ -356,7 +369,7 @@ def conv_backward(hip: Hip, x: torch.Tensor, Wk: torch.Tensor, dy: torch.Tensor,
                   temporal: bool = False, need_dx: bool = True, need_dw: bool = True):
     """Backward of the stride-1 implicit-GEMM convolutions of `wiw_gemm_bf16`: 3x3 pad 1 (ResnetBlock2D convs, resnet.py:269,285)
     or, temporal=True, (3,1,1) pad 1 over T (TemporalResnetBlock, resnet.py:570-592).  x [M, Cin] token-major, Wk [Cout, taps*Cin]
-    in the kernel's layout ([Cout][ky][kx][Cin] / [Cout][kt][Cin]), dy [M, Cout]; Cin, Cout, M % 64 == 0.
+    in the kernel's layout ([Cout][ky][kx][Cin] / [Cout][kt][Cin]), dy [M, Cout]; Cin, Cout % 64 == 0, any M (4 x 7 x 7 = 196).
         dx  = the SAME convolution of dy with the taps mirrored and the channel roles swapped (W2[ci][tap'][co] = W[co][tap][ci])
         dW  = dy^T . im2col(x)   (fp32 [Cout, taps*Cin]: `wgrad` with the im2col operand built in the layout its plan reads)
         db  = column sums of dy
@@ -366,7 +379,7 @@ def conv_backward(hip: Hip, x: torch.Tensor, Wk: torch.Tensor, dy: torch.Tensor,
     M, Cin = x.shape
     Cout = Wk.shape[0]
     taps = 3 if temporal else 9
-    assert Wk.shape == (Cout, taps * Cin) and dy.shape == (M, Cout) and M % 8 == 0 and Cin % 64 == 0 and Cout % 64 == 0
+    assert Wk.shape == (Cout, taps * Cin) and dy.shape == (M, Cout) and Cin % 64 == 0 and Cout % 64 == 0
     dev, dt = hip.device, hip.dtype
     dx = None
     if need_dx:

@@ -37,6 +37,10 @@ class Tape:
         self.after_op = None                          # hook: called after every backward closure (gradient hand-over)
 
     def add(self, t: torch.Tensor, g: torch.Tensor) -> None:
+        # a level of fewer than 64 rows (4 frames of a 3 x 5 plane) mixes tensors of exactly M rows with 16-bit GEMM outputs whose
+        # rows are padded to 64: a gradient takes the row count of ITS tensor (pad rows zero / dropped)
+        if g.dim() == 2 and t.dim() == 2 and g.shape[0] != t.shape[0] and g.shape[1] == t.shape[1]:
+            g = _pad_like(g, t) if g.shape[0] < t.shape[0] else g[: t.shape[0]]
         k = id(t)
         if k not in self.g:
             self.g[k] = g
@@ -79,6 +83,19 @@ def _pad_rows(t: torch.Tensor, mult: int = 64) -> torch.Tensor:
 
 
 TRAIN_MAX_FRAMES = 16   # `self_attention` pads the temporal sequences to Tp = 16 rows
+
+
+def attn_padded_rows(S: int) -> int:
+    """Which form the SPATIAL self-attention of an S-token level takes in the training graph.  0: the dense launches
+    (`attn_spatial` on V^T and `attn_backward` with Sp = S: both need S % 16 == 0).  Otherwise the row stride Sp = 16 ceil(S / 16)
+    of the padded form (`Hip.attn_padded`: every sequence re-ordered to Sp rows, `attn_small` forward, the one-wave backward
+    with Sp > S) — the levels of a 56 x 56 latent with 196 and 49 tokens, of a 24 x 40 one with 60 and 15."""
+    return 0 if S % 16 == 0 else -(-S // 16) * 16
+
+
+def attn_level_plan(h: int, w: int, levels: int = 4):
+    """[(S, Sp)] of the UNet's levels at an h x w latent (Sp as `attn_padded_rows`; each level halves both sides)."""
+    return [((h >> i) * (w >> i), attn_padded_rows((h >> i) * (w >> i))) for i in range(levels)]
 
 
 class UNetTrain:
@@ -372,6 +389,16 @@ class UNetTrain:
                 tape.add(qkv, hip.row_map(dq_seq, hip.ROW_SEQ_TO_T, M, 3 * C, T=T, Tp=Tp, S=Ssp))
             tape.ops.append(bwd)
             return o
+        if attn_padded_rows(S):                                            # S % 16 != 0: pad -> attend -> unpad
+            o, saved = hip.attn_padded(qkv, seqs, S, heads, 0.125)
+
+            def bwd():
+                do = tape.take(o, self.dt)
+                if do is not None:
+                    dq = hip.attn_padded_backward(saved, do)
+                    tape.add(qkv, dq if qkv.shape[0] == M else _pad_like(dq, qkv))
+            tape.ops.append(bwd)
+            return o
         vt = torch.empty(C, M, dtype=self.dt, device=self.device)
         hip.transpose(qkv, 3 * C, 2 * C, M, C, vt, M)
         o = torch.empty(M, C, dtype=self.dt, device=self.device)
@@ -479,7 +506,7 @@ class UNetTrain:
         """x + vec[row // rows_per_vec] (vec fp32 [units, C]): a 1x... broadcast add through the GEMM-free path."""
         hip, tape = self.hip, self.tape
         rep = vec.to(self.dt).repeat_interleave(rows_per_vec, dim=0).contiguous()      # plumbing: broadcast copy
-        y = hip.axpby(x, 1.0, rep, 1.0)
+        y = hip.axpby(x[: rep.shape[0]], 1.0, rep, 1.0)                                 # (x may carry pad rows: M < 64)
 
         def bwd():
             dy = tape.take(y, self.dt)

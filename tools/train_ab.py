@@ -9,12 +9,12 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import wiw_amd  # noqa: F401,E402
 from wiw_amd import train as T  # noqa: E402
 from wiw_amd.config import UNetConfig  # noqa: E402
-from wiw_amd.train_unet import Trainer, UNetTrain  # noqa: E402
+from wiw_amd.train_unet import Trainer, make_unet_train  # noqa: E402
 from wiw_amd.weights import random_state_dict_torch  # noqa: E402
 
 dev = torch.device("cuda:0")
 cfg = UNetConfig()
-net = UNetTrain(cfg, random_state_dict_torch(cfg, 0, dev, torch.float32), dev)
+net = make_unet_train(cfg, random_state_dict_torch(cfg, 0, dev, torch.float32), dev)
 tr = Trainer(net, lr=1e-5)
 gen = torch.Generator().manual_seed(0)
 Tn, h, w = 14, 72, 128

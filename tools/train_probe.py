@@ -9,7 +9,13 @@ norm kernels on their own (ms and GB/s over the trainer's own gradient tensors).
 `--manip448` measures the fine-tuning step of the served network on a 448 x 448 x 14 manipulation clip (56 x 56 latent: levels of
 3136, 784, 196 and 49 tokens, 10 action channels): forward / backward / whole `Trainer.step` ms, peak memory, the kernel-family
 rows `Hip._timed` keeps, the GEMMs by mode, and every attention call by sequence length — the padded form (`attn_small` + the
-one-wave backward at S = 196 and 49) and the one-wave backward at S = 784 next to the LDS-tiled S = 3136."""
+one-wave backward at S = 196 and 49) and the one-wave backward at S = 784 next to the LDS-tiled S = 3136.
+
+`--frames N` (1 .. 32) runs the same measurement at N frames on the tape `make_unet_train` picks (`UNetTrain` up to 16 frames,
+`UNetTrain32` above): a PH x PW x N navigation clip, or with `--manip448` a 448 x 448 x N manipulation clip.  Its record also
+carries `temporal_attention`: the GPU time between the first and the last launch of every temporal self-attention — forward
+(the 32-slot kernel; on the 16-row tape re-ordering, V^T and `attn_small`) and backward closure (row maps, transposes, the two
+one-wave kernels) — and its share of the step."""
 import argparse
 import collections
 import os
@@ -23,7 +29,7 @@ import wiw_amd  # noqa: F401,E402
 from wiw_amd import train as T  # noqa: E402
 from wiw_amd.config import UNetConfig  # noqa: E402
 from wiw_amd.hip import EPI_OUT_F32  # noqa: E402
-from wiw_amd.train_unet import UNetTrain  # noqa: E402
+from wiw_amd.train_unet import UNetTrain, make_unet_train  # noqa: E402
 from wiw_amd.weights import random_state_dict_torch  # noqa: E402
 
 dev = torch.device("cuda:0")
@@ -209,18 +215,23 @@ def clip_cost(max_grad_norm: float, steps: int = 5, dtype=torch.bfloat16):
                       "table_uploads_total": net.hip.sumsq_table_uploads}))
 
 
-def manip448_step(dtype=torch.bfloat16, steps: int = 5):
+def train_step_probe(Tn: int, manip448: bool, dtype=torch.bfloat16, steps: int = 5):
+    """forward / backward / whole `Trainer.step` of the served network on a Tn-frame clip: 448 x 448 manipulation (10 action
+    channels) or PH x PW navigation (Tn action channels)."""
     import json
     import statistics
 
     import numpy as np
 
-    from wiw_amd.pipeline import SCENE_BOUNDS, manip_action_ids
+    from wiw_amd.pipeline import SCENE_BOUNDS, action_ids_idx_encode, manip_action_ids
     from wiw_amd.train_unet import Trainer, attn_level_plan
 
-    Tn, h, w = 14, 56, 56
-    cfg = UNetConfig(num_frames=Tn, action_input_channel=10, task_type="manipulation")
-    net = UNetTrain(cfg, random_state_dict_torch(cfg, 0, dev, torch.float32), dev, dtype=dtype)
+    h, w = (56, 56) if manip448 else (H // 8, W // 8)
+    if manip448:
+        cfg = UNetConfig(num_frames=Tn, action_input_channel=10, task_type="manipulation")
+    else:
+        cfg = UNetConfig(num_frames=Tn, action_input_channel=Tn)
+    net = make_unet_train(cfg, random_state_dict_torch(cfg, 0, dev, torch.float32), dev, dtype=dtype)
     hip = net.hip
     gen = torch.Generator().manual_seed(100)
     rs = np.random.RandomState(0)
@@ -228,9 +239,10 @@ def manip448_step(dtype=torch.bfloat16, steps: int = 5):
     poses[..., :3] = SCENE_BOUNDS[:3] + (SCENE_BOUNDS[3:] - SCENE_BOUNDS[:3]) * rs.uniform(0.1, 0.9, size=(1, Tn, 3))
     poses[..., 3:7] = rs.standard_normal((1, Tn, 4))
     poses[..., 7] = rs.choice([0.0, 1.0], size=(1, Tn))
+    ids = manip_action_ids(poses) if manip448 else action_ids_idx_encode(np.array([[4] + [[1, 2, 1, 3][i % 4] for i in range(Tn - 1)]]))
     lat, noise = torch.randn(1, Tn, 4, h, w, generator=gen) * 0.8, torch.randn(1, Tn, 4, h, w, generator=gen)
     st = T.prepare_step(lat, noise, 1.3, torch.randn(1, 4, h, w, generator=gen), torch.randn(1, 1, 1024, generator=gen), 0.04,
-                        torch.from_numpy(manip_action_ids(poses)))
+                        torch.from_numpy(ids))
     T.clear_wgrad_plans()
     tr = Trainer(net, lr=1e-5, autotune=True)
     for _ in range(2):                                   # warm-up: weight-gradient plans, allocator
@@ -268,8 +280,42 @@ def manip448_step(dtype=torch.bfloat16, steps: int = 5):
     awrap("attn_spatial", lambda a, k: f"S={a[8]}" + (" +lse" if k.get("lse") is not None else ""))
     awrap("attn_small", lambda a, k: f"S={a[8]} Sp={a[9]}")
     awrap("attn_backward", lambda a, k: f"S={a[4]} Sp={k.get('Sp') or a[4]}" + (" given lse" if k.get("lse") is not None else ""))
+    # the temporal self-attentions as a whole: events around the forward's launches after the q|k|v GEMM, and around the
+    # backward closure the call leaves on the tape
+    trecs, in_temporal = [], [False]
+
+    def timed(label, f):
+        def g(*a, **k):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(); out = f(*a, **k); e1.record()
+            trecs.append((label, e0, e1))
+            return out
+        return g
+
+    def fwd_only(name):
+        f = getattr(hip, name)
+        tf = timed("forward", f)
+        setattr(hip, name, lambda *a, **k: (tf if in_temporal[0] else f)(*a, **k))
+    for nm in ("attn_temporal32", "attn_small", "row_map", "transpose"):
+        fwd_only(nm)
+    self_attention = net.self_attention
+
+    def sa(*a, temporal_T=0, **k):
+        in_temporal[0] = bool(temporal_T)
+        try:
+            out = self_attention(*a, temporal_T=temporal_T, **k)
+        finally:
+            in_temporal[0] = False
+        if temporal_T:
+            net.tape.ops[-1] = timed("backward", net.tape.ops[-1])
+        return out
+    net.self_attention = sa
     hip.kernel_profile, hip.gemm_profile = [], []
     ms_prof, _ = wall(lambda: tr.step(st))
+    net.self_attention = self_attention
+    ta = collections.defaultdict(lambda: [0, 0.0])
+    for key, e0, e1 in trecs:
+        ta[key][0] += 1; ta[key][1] += e0.elapsed_time(e1)
     fam = collections.defaultdict(lambda: [0, 0.0])
     for e0, e1, family, _, _ in hip.kernel_profile:
         fam[family][0] += 1; fam[family][1] += e0.elapsed_time(e1)
@@ -283,7 +329,10 @@ def manip448_step(dtype=torch.bfloat16, steps: int = 5):
     step_ms = statistics.median(whole)
     rows = lambda d: {k: {"calls": n, "ms": round(ms, 3), "share_of_step": round(ms / step_ms, 4)}  # noqa: E731
                       for k, (n, ms) in sorted(d.items(), key=lambda kv: -kv[1][1])}
-    print(json.dumps({"probe": "manip448_train_step", "size": f"448x448x{Tn}", "latent": [h, w], "dtype": str(dtype),
+    ta_ms = sum(ms for _, ms in ta.values())
+    print(json.dumps({"probe": "manip448_train_step" if manip448 else "train_step", "size": f"{8 * h}x{8 * w}x{Tn}", "latent": [h, w],
+                      "dtype": str(dtype), "tape": type(net).__name__,
+                      "temporal_attention": dict(rows(ta), total_ms=round(ta_ms, 3), share_of_step=round(ta_ms / step_ms, 4)),
                       "levels_S_Sp": attn_level_plan(h, w), "forward_ms": round(statistics.median(fwd), 2),
                       "backward_ms": round(statistics.median(bwd), 2), "step_ms": round(step_ms, 2),
                       "step_ms_all": [round(x, 1) for x in whole], "step_ms_with_events": round(ms_prof, 1),
@@ -295,12 +344,16 @@ if __name__ == "__main__":
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--max_grad_norm", type=float, default=None, help="measure the cost of global-norm gradient clipping at this "
                     "threshold (the reference's DeepSpeed config uses 0.5) instead of the operator / sweep probes")
-    ap.add_argument("--manip448", action="store_true", help="time the fine-tuning step on a 448 x 448 x 14 manipulation clip")
-    ap.add_argument("--steps", type=int, default=5, help="--max_grad_norm / --manip448: timed steps per block")
+    ap.add_argument("--manip448", action="store_true", help="time the fine-tuning step on a 448 x 448 manipulation clip (14 frames "
+                    "unless --frames says otherwise)")
+    ap.add_argument("--frames", type=int, default=None, help="time the fine-tuning step at this many frames (1 .. 32; above 16 the "
+                    "32-slot tape): a PH x PW navigation clip, or the --manip448 one")
+    ap.add_argument("--steps", type=int, default=5, help="--max_grad_norm / --manip448 / --frames: timed steps per block")
     ap.add_argument("--dtype", choices=["bf16", "fp16"], default="bf16")
     args = ap.parse_args()
-    if args.manip448:
-        manip448_step(torch.float16 if args.dtype == "fp16" else torch.bfloat16, args.steps)
+    if args.manip448 or args.frames is not None:
+        train_step_probe(14 if args.frames is None else args.frames, args.manip448,
+                         torch.float16 if args.dtype == "fp16" else torch.bfloat16, args.steps)
         sys.exit(0)
     if args.max_grad_norm is not None:
         clip_cost(args.max_grad_norm, args.steps, torch.float16 if args.dtype == "fp16" else torch.bfloat16)

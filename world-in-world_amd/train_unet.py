@@ -22,7 +22,7 @@ import torch
 from .config import UNetConfig
 from .hip import A_CONV3X3, A_CONV3X3_S2, A_CONV_T3, EPI_OUT_F32, Hip
 from .train import conv_backward, linear_backward
-from .unet import CIN_PAD, sinusoid
+from .unet import CIN_PAD, MAX_NUM_FRAMES, sinusoid
 
 SMALL = 1 << 16      # gradients of tensors up to this many elements are accumulated in fp32 on the host side of the tape
 
@@ -99,12 +99,17 @@ def attn_level_plan(h: int, w: int, levels: int = 4):
 
 
 class UNetTrain:
+    MAX_FRAMES = TRAIN_MAX_FRAMES   # the frame limit of THIS tape (`UNetTrain32`: 32); `make_unet_train` picks the class
+
+    def _check_frames(self, cfg: UNetConfig) -> None:
+        if cfg.num_frames > self.MAX_FRAMES:
+            raise ValueError(f"num_frames = {cfg.num_frames}: UNetTrain is built for at most {TRAIN_MAX_FRAMES} frames (the "
+                             f"temporal self-attention and its backward pad every site's sequence to {TRAIN_MAX_FRAMES} rows); "
+                             f"UNetTrain32 (or make_unet_train, which chooses) fine-tunes the longer served horizons")
+
     def __init__(self, cfg: UNetConfig, state_dict: Dict[str, torch.Tensor], device="cuda:0", hip: Optional[Hip] = None,
                  dtype: torch.dtype = torch.bfloat16):
-        if cfg.num_frames > TRAIN_MAX_FRAMES:
-            raise ValueError(f"num_frames = {cfg.num_frames}: fine-tuning is built for at most {TRAIN_MAX_FRAMES} frames (the "
-                             f"temporal self-attention and its backward pad every site's sequence to {TRAIN_MAX_FRAMES} rows); "
-                             f"longer horizons are served by UNetHIP only")
+        self._check_frames(cfg)
         self.cfg = cfg
         self.device = torch.device(device)
         self.hip = hip or Hip(self.device, dtype)
@@ -604,6 +609,54 @@ class UNetTrain:
             inv = 1.0 / loss_scale
             self.grads = {k: v.float() * inv for k, v in self.grads.items()}
         return self.grads
+
+
+class UNetTrain32(UNetTrain):
+    """The tape for 1 .. 32 frames (17 .. 32: the longer served horizons, 25 = SVD-XT).  Only the temporal self-attention
+    differs from `UNetTrain`: its forward is `wiw_attn_temporal32_bf16` — the kernel the served 17-32-frame UNet runs — straight
+    on the q|k|v GEMM output in the tape's own (b, t, s) row order (no re-ordering, no V^T, nothing saved but qkv and O); its
+    backward re-orders qkv, O and dO to per-site sequences of 32 slots and runs the one-wave backward with Sp = 32."""
+
+    MAX_FRAMES = MAX_NUM_FRAMES
+
+    def _check_frames(self, cfg: UNetConfig) -> None:
+        if not 1 <= cfg.num_frames <= self.MAX_FRAMES:
+            raise ValueError(f"num_frames = {cfg.num_frames}: UNetTrain32 fine-tunes 1 .. {self.MAX_FRAMES} frames (its temporal "
+                             f"self-attention holds every site's sequence in {self.MAX_FRAMES} slots)")
+
+    def self_attention(self, a, p, M, seqs, S, heads, temporal_T=0):
+        if not temporal_T:
+            return super().self_attention(a, p, M, seqs, S, heads)
+        hip, tape = self.hip, self.tape
+        C = heads * 64
+        qkv = self.linear(a, p + ".to_qkv", M, bias=False, wkey=p + ".to_qkv.weight",
+                          split=(p + ".to_q.weight", p + ".to_k.weight", p + ".to_v.weight"))
+        T, Tp, Ssp = temporal_T, 32, M // (seqs * temporal_T)             # seqs = batch items here
+        nseq = seqs * Ssp
+        Ms = nseq * Tp
+        o = torch.empty(M, C, dtype=self.dt, device=self.device)
+        hip.attn_temporal32(qkv, 3 * C, o, C, seqs, T, Ssp, heads, 0.125)
+
+        def bwd():
+            do = tape.take(o, self.dt)
+            if do is None:
+                return
+            # T_TO_SEQ writes zeros into the slots T .. 31 of every sequence; the backward leaves zeros in those rows of
+            # d_qkv, and SEQ_TO_T drops them
+            q_seq = hip.row_map(qkv, hip.ROW_T_TO_SEQ, Ms, 3 * C, T=T, Tp=Tp, S=Ssp)
+            o_seq = hip.row_map(o, hip.ROW_T_TO_SEQ, Ms, C, T=T, Tp=Tp, S=Ssp)
+            do_seq = hip.row_map(do, hip.ROW_T_TO_SEQ, Ms, C, T=T, Tp=Tp, S=Ssp)
+            dq_seq = hip.attn_backward(q_seq, o_seq, do_seq, nseq, T, heads, 0.125, Sp=Tp)
+            tape.add(qkv, hip.row_map(dq_seq, hip.ROW_SEQ_TO_T, M, 3 * C, T=T, Tp=Tp, S=Ssp))
+        tape.ops.append(bwd)
+        return o
+
+
+def make_unet_train(cfg: UNetConfig, state_dict: Dict[str, torch.Tensor], device="cuda:0", hip: Optional[Hip] = None,
+                    dtype: torch.dtype = torch.bfloat16) -> UNetTrain:
+    """The tape for `cfg`: `UNetTrain` up to 16 frames (unchanged behaviour for every existing user), `UNetTrain32` above."""
+    cls = UNetTrain if cfg.num_frames <= TRAIN_MAX_FRAMES else UNetTrain32
+    return cls(cfg, state_dict, device, hip=hip, dtype=dtype)
 
 
 class EMAShadow:

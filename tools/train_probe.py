@@ -15,7 +15,12 @@ one-wave backward at S = 196 and 49) and the one-wave backward at S = 784 next t
 `UNetTrain32` above): a PH x PW x N navigation clip, or with `--manip448` a 448 x 448 x N manipulation clip.  Its record also
 carries `temporal_attention`: the GPU time between the first and the last launch of every temporal self-attention — forward
 (the 32-slot kernel; on the 16-row tape re-ordering, V^T and `attn_small`) and backward closure (row maps, transposes, the two
-one-wave kernels) — and its share of the step."""
+one-wave kernels) — and its share of the step.
+
+`--gradient_checkpointing` (with `--frames N` and / or `--manip448`) measures what activation checkpointing costs and saves: one
+tape in one process, blocks of `--steps` steps without and with the keyword in alternation (off, on, off, on); per mode forward,
+backward and whole `Trainer.step` ms and the peak GiB (`torch.cuda.max_memory_allocated`, reset per block), the checkpointed step
+against `plain step + 1.15 x plain forward`; written to profiles/r25a_train_step_ckpt_<size>x<frames>_<dtype>.json."""
 import argparse
 import collections
 import os
@@ -340,6 +345,96 @@ def train_step_probe(Tn: int, manip448: bool, dtype=torch.bfloat16, steps: int =
                       "kernel_families": rows(fam), "gemms": rows(gm), "wgrad_plans": len(T.wgrad_plans())}))
 
 
+def _probe_clip(Tn: int, manip448: bool):
+    """(cfg, latent (h, w), StepInputs) of the clip `train_step_probe` measures."""
+    import numpy as np
+
+    from wiw_amd.pipeline import SCENE_BOUNDS, action_ids_idx_encode, manip_action_ids
+
+    h, w = (56, 56) if manip448 else (H // 8, W // 8)
+    if manip448:
+        cfg = UNetConfig(num_frames=Tn, action_input_channel=10, task_type="manipulation")
+    else:
+        cfg = UNetConfig(num_frames=Tn, action_input_channel=Tn)
+    gen = torch.Generator().manual_seed(100)
+    rs = np.random.RandomState(0)
+    poses = np.zeros((1, Tn, 8), np.float32)
+    poses[..., :3] = SCENE_BOUNDS[:3] + (SCENE_BOUNDS[3:] - SCENE_BOUNDS[:3]) * rs.uniform(0.1, 0.9, size=(1, Tn, 3))
+    poses[..., 3:7] = rs.standard_normal((1, Tn, 4))
+    poses[..., 7] = rs.choice([0.0, 1.0], size=(1, Tn))
+    ids = manip_action_ids(poses) if manip448 else action_ids_idx_encode(np.array([[4] + [[1, 2, 1, 3][i % 4] for i in range(Tn - 1)]]))
+    lat, noise = torch.randn(1, Tn, 4, h, w, generator=gen) * 0.8, torch.randn(1, Tn, 4, h, w, generator=gen)
+    st = T.prepare_step(lat, noise, 1.3, torch.randn(1, 4, h, w, generator=gen), torch.randn(1, 1, 1024, generator=gen), 0.04,
+                        torch.from_numpy(ids))
+    return cfg, (h, w), st
+
+
+def checkpoint_cost(Tn: int, manip448: bool, dtype=torch.bfloat16, steps: int = 5):
+    """Activation checkpointing off / on / off / on on ONE tape (the keyword is configuration: `forward` reads it)."""
+    import json
+    import statistics
+
+    from wiw_amd.train_unet import Trainer
+
+    cfg, (h, w), st = _probe_clip(Tn, manip448)
+    net = make_unet_train(cfg, random_state_dict_torch(cfg, 0, dev, torch.float32), dev, dtype=dtype)
+    hip = net.hip
+    T.clear_wgrad_plans()
+    tr = Trainer(net, lr=1e-5, autotune=True)
+    for mode in (False, False, True):                     # warm-up: weight-gradient plans, allocator, both modes
+        net.gradient_checkpointing = mode
+        tr.step(st)
+
+    def wall(fn):
+        torch.cuda.synchronize(); t0 = time.perf_counter()
+        out = fn()
+        torch.cuda.synchronize()
+        return 1e3 * (time.perf_counter() - t0), out
+
+    blocks = []
+    for mode in (False, True, False, True):
+        net.gradient_checkpointing = mode
+        torch.cuda.synchronize()
+        torch.cuda.reset_peak_memory_stats()
+        fwd, bwd, whole, held = [], [], [], []
+        for _ in range(steps):
+            net.grads = {}                                # the last step's gradients: `forward` drops them, it does not hold them
+            before = torch.cuda.memory_allocated()
+            ms, pred = wall(lambda: net.forward(st.unet_input, st.timestep, st.ehs, st.added_time_ids, st.action_ids))
+            fwd.append(ms)
+            held.append((torch.cuda.memory_allocated() - before) / 2 ** 30)
+            loss, dpred = T.TrainStep(hip).loss_and_grad(pred, st)
+            bwd.append(wall(lambda: net.backward(dpred.reshape(pred.shape), tr.loss_scale))[0])
+            del pred, dpred
+        for _ in range(steps):
+            whole.append(wall(lambda: tr.step(st))[0])
+        blocks.append({"gradient_checkpointing": mode, "forward_ms": round(statistics.median(fwd), 2),
+                       "backward_ms": round(statistics.median(bwd), 2), "step_ms": round(statistics.median(whole), 2),
+                       "step_ms_all": [round(x, 1) for x in whole], "peak_GiB": round(torch.cuda.max_memory_allocated() / 2 ** 30, 2),
+                       "held_after_forward_GiB": round(statistics.median(held), 2)})
+
+    def mode_row(mode):
+        bs = [b for b in blocks if b["gradient_checkpointing"] is mode]
+        return {"forward_ms": round(statistics.median(b["forward_ms"] for b in bs), 2),
+                "backward_ms": round(statistics.median(b["backward_ms"] for b in bs), 2),
+                "step_ms": round(statistics.median(x for b in bs for x in b["step_ms_all"]), 2),
+                "peak_GiB": max(b["peak_GiB"] for b in bs), "held_after_forward_GiB": max(b["held_after_forward_GiB"] for b in bs)}
+    off, on = mode_row(False), mode_row(True)
+    budget = off["step_ms"] + 1.15 * off["forward_ms"]
+    rec = {"probe": "gradient_checkpointing", "size": f"{8 * h}x{8 * w}x{Tn}", "latent": [h, w], "dtype": str(dtype),
+           "tape": type(net).__name__, "task": cfg.task_type, "steps_per_block": steps, "off": off, "on": on,
+           "step_on_over_off": round(on["step_ms"] / off["step_ms"], 4), "peak_on_over_off": round(on["peak_GiB"] / off["peak_GiB"], 4),
+           "budget_ms_plain_step_plus_1.15_plain_forward": round(budget, 2), "step_on_over_budget": round(on["step_ms"] / budget, 4),
+           "weights_moments_grads_GiB": round(sum(v.numel() for v in net.master.values()) * (4 * 4 + 2) / 2 ** 30, 2),
+           "loss_scale": tr.loss_scale, "blocks": blocks}
+    print(json.dumps(rec))
+    out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
+                       f"r25a_train_step_ckpt_{8 * h}x{8 * w}x{Tn}_{'fp16' if dtype == torch.float16 else 'bf16'}.json")
+    with open(out, "w") as f:
+        json.dump(rec, f, indent=1)
+        f.write("\n")
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--max_grad_norm", type=float, default=None, help="measure the cost of global-norm gradient clipping at this "
@@ -348,9 +443,18 @@ if __name__ == "__main__":
                     "unless --frames says otherwise)")
     ap.add_argument("--frames", type=int, default=None, help="time the fine-tuning step at this many frames (1 .. 32; above 16 the "
                     "32-slot tape): a PH x PW navigation clip, or the --manip448 one")
+    ap.add_argument("--gradient_checkpointing", action="store_true", help="with --frames / --manip448: the step without and with "
+                    "activation checkpointing (off, on, off, on): forward / backward / step ms and peak GiB per mode, written to "
+                    "profiles/r25a_train_step_ckpt_<size>x<frames>_<dtype>.json")
     ap.add_argument("--steps", type=int, default=5, help="--max_grad_norm / --manip448 / --frames: timed steps per block")
     ap.add_argument("--dtype", choices=["bf16", "fp16"], default="bf16")
     args = ap.parse_args()
+    if args.gradient_checkpointing:
+        if not (args.manip448 or args.frames is not None):
+            ap.error("--gradient_checkpointing needs --frames N and / or --manip448")
+        checkpoint_cost(14 if args.frames is None else args.frames, args.manip448,
+                        torch.float16 if args.dtype == "fp16" else torch.bfloat16, args.steps)
+        sys.exit(0)
     if args.manip448 or args.frames is not None:
         train_step_probe(14 if args.frames is None else args.frames, args.manip448,
                          torch.float16 if args.dtype == "fp16" else torch.bfloat16, args.steps)

@@ -14,7 +14,7 @@ re-layouts) are PyTorch plumbing.  Pinned by `tests/golden/train_step_tiny*.npz`
 from __future__ import annotations
 
 import math
-from typing import Dict, List, Optional
+from typing import Dict, Optional
 
 import numpy as np
 import torch
@@ -33,8 +33,10 @@ class Tape:
 
     def __init__(self, hip: Hip):
         self.hip, self.ops, self.g = hip, [], {}
-        self.keep: List[torch.Tensor] = []            # tensors whose id() is a key must stay alive
+        self.keep: Dict[int, torch.Tensor] = {}       # tensors whose id() is a key must stay alive
         self.after_op = None                          # hook: called after every backward closure (gradient hand-over)
+        self.segmented = False                        # `segment` was used: a tensor leaves `keep` with its gradient (below)
+        self._diverted = False                        # inside the first pass of a segment
 
     def add(self, t: torch.Tensor, g: torch.Tensor) -> None:
         # a level of fewer than 64 rows (4 frames of a 3 x 5 plane) mixes tensors of exactly M rows with 16-bit GEMM outputs whose
@@ -44,7 +46,7 @@ class Tape:
         k = id(t)
         if k not in self.g:
             self.g[k] = g
-            self.keep.append(t)
+            self.keep[k] = t
         elif g.numel() <= SMALL or g.dtype == torch.float32:
             self.g[k] = (self.g[k].float() + g.float())
         else:
@@ -52,6 +54,8 @@ class Tape:
 
     def take(self, t: torch.Tensor, dtype=None) -> Optional[torch.Tensor]:
         g = self.g.pop(id(t), None)
+        if self.segmented:                             # a recomputed activation must not outlive its closure: `keep` would
+            self.keep.pop(id(t), None)                 # otherwise collect every segment's tensors until the end of `run`
         if g is not None and dtype is not None and g.dtype != dtype:
             g = g.to(dtype)
         return g
@@ -63,6 +67,36 @@ class Tape:
             if self.after_op is not None:
                 self.after_op()
         self.release()
+
+    def segment(self, fn):
+        """Activation checkpointing of one stretch of the forward.  y = fn() runs NOW with its closures diverted to a list that
+        is dropped on return: nothing fn allocated survives but y.  ONE closure goes on the tape, holding fn (and through it fn's
+        input tensors, by reference) and y.  In the backward it runs fn again, recording on the tape itself — fn's closures land
+        on top of `ops`, where `run` pops them as if they had always been there, against the same `g` map: the order of every
+        fan-in add (16-bit roundings) is that of the plain run — and moves the pending gradient of y to the recomputed y'.
+        fn must be repeatable bit for bit (the kernels are: DESIGN.md 5) and must reach its inputs as the SAME tensor objects
+        both times: gradients are keyed by identity.  Segments do not nest."""
+        assert not self._diverted, "Tape.segment does not nest"
+        self.segmented = True
+        real, self.ops, self._diverted = self.ops, [], True
+        try:
+            y = fn()
+        finally:
+            self.ops, self._diverted = real, False       # the diverted closures and what they saved are dropped here
+        held = [y]
+
+        def recompute():
+            k = id(held[0])
+            if k not in self.g:                            # nothing flows into y: every closure of fn would find no gradient
+                held.clear()
+                return
+            y2 = fn()                                      # closures on top of `ops`; y2 is referenced by the last of them
+            self.g[id(y2)] = self.g.pop(k)
+            self.keep[id(y2)] = y2
+            del self.keep[k]
+            held.clear()                                   # y is dropped (its consumers' closures have run)
+        self.ops.append(recompute)
+        return y
 
     def release(self) -> None:
         """Break the tape <-> closure reference cycles NOW: the saved activations of a step (55 GiB at 576x1024x14) must not
@@ -108,8 +142,14 @@ class UNetTrain:
                              f"UNetTrain32 (or make_unet_train, which chooses) fine-tunes the longer served horizons")
 
     def __init__(self, cfg: UNetConfig, state_dict: Dict[str, torch.Tensor], device="cuda:0", hip: Optional[Hip] = None,
-                 dtype: torch.dtype = torch.bfloat16):
+                 dtype: torch.dtype = torch.bfloat16, gradient_checkpointing: bool = False):
         self._check_frames(cfg)
+        if not isinstance(gradient_checkpointing, bool):
+            raise TypeError(f"gradient_checkpointing must be a bool, not {type(gradient_checkpointing).__name__}")
+        # `--gradient_checkpointing` (train_svd.py:211-215, 628-629): every ResBlock and every transformer of `forward` keeps only
+        # its output and is run again in the backward (`Tape.segment`).  Configuration, not state: the gradients are the plain
+        # run's bit for bit, checkpoints do not record it
+        self.gradient_checkpointing = gradient_checkpointing
         self.cfg = cfg
         self.device = torch.device(device)
         self.hip = hip or Hip(self.device, dtype)
@@ -521,6 +561,13 @@ class UNetTrain:
         tape.ops.append(bwd)
         return y
 
+    def _segment(self, block, *args):
+        """One ResBlock / transformer of `forward`: as it is, or under `gradient_checkpointing` as one recomputed segment of the
+        tape.  args are bound here, once: both passes see the same tensor objects (emb_silu, ehs16, skips, the residual input)."""
+        if not self.gradient_checkpointing:
+            return block(*args)
+        return self.tape.segment(lambda: block(*args))
+
     # ------------------------------------------------------------------------------------------
     # the network
     # ------------------------------------------------------------------------------------------
@@ -564,29 +611,29 @@ class UNetTrain:
             has_attn = i < n - 1
             eps = 1e-6 if has_attn else 1e-5
             for j in range(L):
-                x = self.res_block(f"{p}.resnets.{j}", x, C, ch[i], M, H, W, T, emb_silu, eps)
+                x = self._segment(self.res_block, f"{p}.resnets.{j}", x, C, ch[i], M, H, W, T, emb_silu, eps)
                 C = ch[i]
                 if has_attn:
-                    x = self.transformer(f"{p}.attentions.{j}", x, C, M, H, W, T, cfg.num_attention_heads[i], ehs16)
+                    x = self._segment(self.transformer, f"{p}.attentions.{j}", x, C, M, H, W, T, cfg.num_attention_heads[i], ehs16)
                 skips.append((x, C))
             if i < n - 1:
                 H, W = H // 2, W // 2
                 M = T * H * W
                 x = self.conv(x, f"{p}.downsamplers.0.conv", M, H, W, mode=A_CONV3X3_S2)
                 skips.append((x, C))
-        x = self.res_block("mid_block.resnets.0", x, C, C, M, H, W, T, emb_silu, 1e-5)
-        x = self.transformer("mid_block.attentions.0", x, C, M, H, W, T, cfg.num_attention_heads[-1], ehs16)
-        x = self.res_block("mid_block.resnets.1", x, C, C, M, H, W, T, emb_silu, 1e-5)
+        x = self._segment(self.res_block, "mid_block.resnets.0", x, C, C, M, H, W, T, emb_silu, 1e-5)
+        x = self._segment(self.transformer, "mid_block.attentions.0", x, C, M, H, W, T, cfg.num_attention_heads[-1], ehs16)
+        x = self._segment(self.res_block, "mid_block.resnets.1", x, C, C, M, H, W, T, emb_silu, 1e-5)
         rch = list(reversed(ch))
         rheads = list(reversed(cfg.num_attention_heads))
         for i in range(n):
             p = f"up_blocks.{i}"
             for j in range(L + 1):
                 sk, Cs = skips.pop()
-                x = self.res_block(f"{p}.resnets.{j}", self.concat(x, sk), C + Cs, rch[i], M, H, W, T, emb_silu, 1e-6)
+                x = self._segment(self.res_block, f"{p}.resnets.{j}", self.concat(x, sk), C + Cs, rch[i], M, H, W, T, emb_silu, 1e-6)
                 C = rch[i]
                 if i > 0:
-                    x = self.transformer(f"{p}.attentions.{j}", x, C, M, H, W, T, rheads[i], ehs16)
+                    x = self._segment(self.transformer, f"{p}.attentions.{j}", x, C, M, H, W, T, rheads[i], ehs16)
             if i < n - 1:
                 x = self.upsample2x(x, M, H, W)
                 H, W = 2 * H, 2 * W
@@ -653,10 +700,10 @@ class UNetTrain32(UNetTrain):
 
 
 def make_unet_train(cfg: UNetConfig, state_dict: Dict[str, torch.Tensor], device="cuda:0", hip: Optional[Hip] = None,
-                    dtype: torch.dtype = torch.bfloat16) -> UNetTrain:
+                    dtype: torch.dtype = torch.bfloat16, gradient_checkpointing: bool = False) -> UNetTrain:
     """The tape for `cfg`: `UNetTrain` up to 16 frames (unchanged behaviour for every existing user), `UNetTrain32` above."""
     cls = UNetTrain if cfg.num_frames <= TRAIN_MAX_FRAMES else UNetTrain32
-    return cls(cfg, state_dict, device, hip=hip, dtype=dtype)
+    return cls(cfg, state_dict, device, hip=hip, dtype=dtype, gradient_checkpointing=gradient_checkpointing)
 
 
 class EMAShadow:

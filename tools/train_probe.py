@@ -20,9 +20,15 @@ one-wave kernels) — and its share of the step.
 `--gradient_checkpointing` (with `--frames N` and / or `--manip448`) measures what activation checkpointing costs and saves: one
 tape in one process, blocks of `--steps` steps without and with the keyword in alternation (off, on, off, on); per mode forward,
 backward and whole `Trainer.step` ms and the peak GiB (`torch.cuda.max_memory_allocated`, reset per block), the checkpointed step
-against `plain step + 1.15 x plain forward`; written to profiles/r25a_train_step_ckpt_<size>x<frames>_<dtype>.json."""
+against `plain step + 1.15 x plain forward`; written to profiles/r25a_train_step_ckpt_<size>x<frames>_<dtype>.json.
+
+`--num_past_obs P` (1 .. 8) measures the step of the served network on a PH x PW x 14 navigation clip with P conditioning tokens
+per sample (`UNetTrain(num_past_obs=P)`): forward / backward / step ms, peak GiB and, above 1, the summed ms of the 32
+cross-attentions — LayerNorm, to_q GEMM, forward kernel, backward kernels — with the backward's bytes/s against its minimum;
+written to profiles/r26a_train_step_ctx_P<P>_<size>x14_<dtype>.json."""
 import argparse
 import collections
+import dataclasses
 import os
 import sys
 import time
@@ -435,6 +441,123 @@ def checkpoint_cost(Tn: int, manip448: bool, dtype=torch.bfloat16, steps: int = 
         f.write("\n")
 
 
+def past_obs_probe(P: int, dtype=torch.bfloat16, steps: int = 5):
+    """`--num_past_obs P`: forward / backward / whole `Trainer.step` of the served network on a PH x PW x 14 navigation clip with
+    P conditioning tokens, peak GiB, and — P > 1 — the 32 cross-attentions of the step by piece: the forward's LayerNorm(norm2),
+    to_q GEMM and `cross_attn_fewkeys` launch, the backward kernels (`cross_attn_fewkeys_backward`: the streaming launch + the
+    block sum) against their 3 x rows x C x 2-byte minimum, and the backward closures of norm2 / to_q.  P = 1 is the row every
+    other measurement of this size has: the same tape, launch for launch."""
+    import json
+    import statistics
+
+    from wiw_amd.train_unet import Trainer
+
+    Tn = 14
+    cfg, (h, w), st = _probe_clip(Tn, False)
+    gen = torch.Generator().manual_seed(101)
+    ehs = torch.randn(1, P, cfg.cross_attention_dim, generator=gen) if P > 1 else st.ehs
+    net = make_unet_train(cfg, random_state_dict_torch(cfg, 0, dev, torch.float32), dev, dtype=dtype, num_past_obs=P)
+    hip = net.hip
+    T.clear_wgrad_plans()
+    tr = Trainer(net, lr=1e-5, autotune=True)
+    st = dataclasses.replace(st, ehs=ehs)
+    for _ in range(2):                                   # warm-up: weight-gradient plans, allocator
+        tr.step(st)
+    torch.cuda.synchronize()
+    torch.cuda.reset_peak_memory_stats()
+
+    def wall(fn):
+        torch.cuda.synchronize(); t0 = time.perf_counter()
+        out = fn()
+        torch.cuda.synchronize()
+        return 1e3 * (time.perf_counter() - t0), out
+
+    fwd, bwd, whole = [], [], []
+    for _ in range(steps):
+        ms, pred = wall(lambda: net.forward(st.unet_input, st.timestep, st.ehs, st.added_time_ids, st.action_ids))
+        fwd.append(ms)
+        loss, dpred = T.TrainStep(hip).loss_and_grad(pred, st)
+        bwd.append(wall(lambda: net.backward(dpred.reshape(pred.shape), tr.loss_scale))[0])
+        del pred, dpred
+    for _ in range(steps):
+        whole.append(wall(lambda: tr.step(st))[0])
+    peak = torch.cuda.max_memory_allocated() / 2 ** 30
+    step_ms = statistics.median(whole)
+    rec = {"probe": "train_step_past_obs", "size": f"{8 * h}x{8 * w}x{Tn}", "latent": [h, w], "dtype": str(dtype),
+           "tape": type(net).__name__, "num_past_obs": P, "forward_ms": round(statistics.median(fwd), 2),
+           "backward_ms": round(statistics.median(bwd), 2), "step_ms": round(step_ms, 2), "step_ms_all": [round(x, 1) for x in whole],
+           "peak_GiB": round(peak, 2), "loss_scale": tr.loss_scale,
+           "optimizer_tensors": len(Trainer.optimizer_shapes(net))}
+    if P > 1:
+        # one more step with events round the pieces of every cross-attention
+        recs, inside = [], [False]
+
+        def timed(label, f):
+            def g(*a, **k):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record(); out = f(*a, **k); e1.record()
+                recs.append((label, e0, e1))
+                return out
+            return g
+
+        def piece(obj, name, label, pick):
+            f = getattr(obj, name)
+            tf = timed(label, f)
+
+            def g(*a, **k):
+                if not (inside[0] and pick(a)):
+                    return f(*a, **k)
+                out = tf(*a, **k)
+                net.tape.ops[-1] = timed(label + " backward closure", net.tape.ops[-1])
+                return out
+            setattr(obj, name, g)
+            return f
+        ln = piece(net, "layernorm", "LayerNorm norm2", lambda a: a[1].endswith(".norm2"))
+        lin = piece(net, "linear", "to_q GEMM", lambda a: a[1].endswith(".attn2.to_q"))
+        kf, kb = hip.cross_attn_fewkeys, hip.cross_attn_fewkeys_backward
+        hip.cross_attn_fewkeys = timed("forward kernel", kf)
+        hip.cross_attn_fewkeys_backward = timed("backward kernels", kb)
+        cross = net.cross_attention
+
+        def ca(*a, **k):
+            inside[0] = True
+            try:
+                return cross(*a, **k)
+            finally:
+                inside[0] = False
+        net.cross_attention = ca
+        hip.kernel_profile = []
+        ms_prof, _ = wall(lambda: tr.step(st))
+        net.cross_attention, net.layernorm, net.linear = cross, ln, lin
+        hip.cross_attn_fewkeys, hip.cross_attn_fewkeys_backward = kf, kb
+        agg = collections.defaultdict(lambda: [0, 0.0])
+        for label, e0, e1 in recs:
+            agg[label][0] += 1; agg[label][1] += e0.elapsed_time(e1)
+        by_c = collections.defaultdict(lambda: [0, 0.0, 0.0])          # the backward kernels by width: calls, ms, minimum bytes
+        for e0, e1, family, _, nbytes in hip.kernel_profile:
+            if family == "attn_cross_bwd":
+                r = by_c[int(nbytes)]
+                r[0] += 1; r[1] += e0.elapsed_time(e1); r[2] += nbytes
+        hip.kernel_profile = None
+        listed = ("LayerNorm norm2", "to_q GEMM", "forward kernel", "backward kernels")
+        total = sum(agg[k][1] for k in listed)
+        rec["cross_attention"] = {
+            "pieces": {k: {"calls": n, "ms": round(ms, 3), "share_of_step": round(ms / step_ms, 4)}
+                       for k, (n, ms) in sorted(agg.items(), key=lambda kv: -kv[1][1])},
+            "listed_pieces": list(listed), "total_ms": round(total, 3), "share_of_step": round(total / step_ms, 4),
+            "total_with_closures_ms": round(sum(ms for _, ms in agg.values()), 3),
+            "backward_kernels_by_minimum_bytes": [{"min_MB_per_call": round(b / 1e6, 2), "calls": n, "ms": round(ms, 3),
+                                                   "GBps_of_minimum": round(tot / ms / 1e6, 1)}
+                                                  for b, (n, ms, tot) in sorted(by_c.items(), reverse=True)],
+            "step_ms_with_events": round(ms_prof, 1)}
+    print(json.dumps(rec))
+    out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
+                       f"r26a_train_step_ctx_P{P}_{8 * h}x{8 * w}x{Tn}_{'fp16' if dtype == torch.float16 else 'bf16'}.json")
+    with open(out, "w") as f:
+        json.dump(rec, f, indent=1)
+        f.write("\n")
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--max_grad_norm", type=float, default=None, help="measure the cost of global-norm gradient clipping at this "
@@ -446,9 +569,15 @@ if __name__ == "__main__":
     ap.add_argument("--gradient_checkpointing", action="store_true", help="with --frames / --manip448: the step without and with "
                     "activation checkpointing (off, on, off, on): forward / backward / step ms and peak GiB per mode, written to "
                     "profiles/r25a_train_step_ckpt_<size>x<frames>_<dtype>.json")
-    ap.add_argument("--steps", type=int, default=5, help="--max_grad_norm / --manip448 / --frames: timed steps per block")
+    ap.add_argument("--num_past_obs", type=int, default=None, help="time the fine-tuning step (PH x PW x 14 navigation) with this many "
+                    "conditioning tokens per sample (1 .. 8) and, above 1, the 32 cross-attentions by piece; written to "
+                    "profiles/r26a_train_step_ctx_P<P>_<size>x14_<dtype>.json")
+    ap.add_argument("--steps", type=int, default=5, help="--max_grad_norm / --manip448 / --frames / --num_past_obs: timed steps per block")
     ap.add_argument("--dtype", choices=["bf16", "fp16"], default="bf16")
     args = ap.parse_args()
+    if args.num_past_obs is not None:
+        past_obs_probe(args.num_past_obs, torch.float16 if args.dtype == "fp16" else torch.bfloat16, args.steps)
+        sys.exit(0)
     if args.gradient_checkpointing:
         if not (args.manip448 or args.frames is not None):
             ap.error("--gradient_checkpointing needs --frames N and / or --manip448")

@@ -213,15 +213,25 @@ EXPORTS = {
                                             C.c_void_p]),
 }
 
+# include/wiw_cross_attn_train.h: the training-side companion header (the backward of the few-keys cross-attention), bound on
+# the same two libraries
+EXPORTS_CROSS_TRAIN = {
+    "wiw_cross_attn_fewkeys_bwd_partials": (C.c_int64, [C.c_int64, C.c_int, C.c_int, C.c_int]),
+    "wiw_cross_attn_fewkeys_bwd_bf16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                                  C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int,
+                                                  C.c_int, C.c_float]),
+}
+
 
 def load_library(path: str = LIB_PATH) -> C.CDLL:
-    """dlopen the C-ABI library and declare every prototype of include/wiw_svd.h.  Raises if absent."""
+    """dlopen the C-ABI library and declare every prototype of include/wiw_svd.h and include/wiw_cross_attn_train.h.  Raises if
+    absent."""
     if not os.path.exists(path):
         raise RuntimeError(
             f"{path} not found: the HIP extension is required (build it with "
             f"`python world-in-world_amd/build.py`); there is no CPU or PyTorch fallback")
     lib = C.CDLL(path)
-    for name, (res, args) in EXPORTS.items():
+    for name, (res, args) in (*EXPORTS.items(), *EXPORTS_CROSS_TRAIN.items()):
         fn = getattr(lib, name)  # AttributeError if the symbol is missing
         fn.restype = res
         fn.argtypes = args
@@ -489,6 +499,25 @@ class Hip:
             self.lib.wiw_cross_attn_fewkeys_bf16(self._stream(), _p(Q), ldq, _p(K), _p(V), _p(O), ldo, rows, rows_per_item, heads, P,
                                                  scale), "wiw_cross_attn_fewkeys_bf16"))
         return O
+
+    def cross_attn_fewkeys_backward(self, Q, ldq, K, V, dO, lddo, rows, rows_per_item, heads, P, scale, dQ=None, lddq=None):
+        """Backward of `cross_attn_fewkeys` (csrc/cross_attn_bwd.hip; the softmax weights are recomputed from Q and K):
+        dO [rows, heads*64] 16-bit -> (dQ 16-bit [rows, heads*64] (or the caller's `dQ` with row stride `lddq`),
+        dK, dV fp32 [rows / rows_per_item, P, heads*64]).  Bit-repeatable."""
+        C_ = heads * 64
+        items = rows // rows_per_item
+        assert K.is_contiguous() and V.is_contiguous() and K.shape == V.shape == (items, P, C_)
+        n = int(self.lib.wiw_cross_attn_fewkeys_bwd_partials(rows, rows_per_item, heads, P))
+        partial = torch.empty(max(n, 4), dtype=torch.float32, device=self.device)
+        if dQ is None:
+            dQ, lddq = torch.empty(rows, C_, dtype=self.dtype, device=self.device), C_
+        dK = torch.empty(items, P, C_, dtype=torch.float32, device=self.device)
+        dV = torch.empty_like(dK)
+        self._timed("attn_cross_bwd", 8.0 * rows * P * C_, 6.0 * rows * C_, lambda: self._ck(
+            self.lib.wiw_cross_attn_fewkeys_bwd_bf16(self._stream(), _p(Q), ldq, _p(K), _p(V), _p(dO), lddo, _p(dQ), lddq, _p(dK),
+                                                     _p(dV), _p(partial), rows, rows_per_item, heads, P, scale),
+            "wiw_cross_attn_fewkeys_bwd_bf16"))
+        return dQ, dK, dV
 
     def attn_small(self, QK, ldqk, k_col_off, Vt, ldvt, O, ldo, seqs, S, Sp, heads, head_dim, scale):
         self._timed("attn_small", 4.0 * seqs * heads * S * S * head_dim, 8.0 * seqs * S * heads * head_dim, lambda: self._ck(

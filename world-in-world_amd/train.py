@@ -123,9 +123,9 @@ def batch_from_pixels(front, pixel_values: torch.Tensor, past_obs: torch.Tensor,
     cond_latents = sample(cond_px, "cond_eps")                                                # * sf / sf
     sigma = float(d["sigma"]) if "sigma" in d else float(rand_log_normal([1], 0.7, 1.6, generator)[0])
     po = past_obs.to(dev, torch.float32)
-    assert po.reshape(-1, *po.shape[-3:]).shape[0] == 1, "one past observation per sample (train_svd.sh; UNetTrain takes (1, 1, D))"
-    e = front._embed(po.reshape(-1, *po.shape[-3:]), None)                                    # (1, 1, D) fp32
-    ehs = e.reshape(1, 1, e.shape[-1])
+    po = po.reshape(-1, *po.shape[-3:])                                                       # (P, 3, H', W'): --num_past_obs P
+    e = front._embed(po, None)                                                                # one embedding per past observation
+    ehs = e.reshape(1, po.shape[0], e.shape[-1])                                              # (1, P, D): UNetTrain(num_past_obs=P)
     action_ids = torch.from_numpy(ids if manip else action_ids_idx_encode(acts))
     random_p = None
     if dropout_prob is not None:

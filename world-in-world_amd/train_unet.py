@@ -142,8 +142,14 @@ class UNetTrain:
                              f"UNetTrain32 (or make_unet_train, which chooses) fine-tunes the longer served horizons")
 
     def __init__(self, cfg: UNetConfig, state_dict: Dict[str, torch.Tensor], device="cuda:0", hip: Optional[Hip] = None,
-                 dtype: torch.dtype = torch.bfloat16, gradient_checkpointing: bool = False):
+                 dtype: torch.dtype = torch.bfloat16, gradient_checkpointing: bool = False, num_past_obs: int = 1):
         self._check_frames(cfg)
+        # `--num_past_obs P` (train_svd.py:359, 889-894): conditioning tokens per sample.  1: the single-key closed form
+        # (`cross_vector`), every launch as it always was.  2 .. 8: both blocks of `transformer` run the general cross-attention
+        # (`cross_attention`) and `forward` takes ehs (1, P, D) — norm2 / attn2.to_q / attn2.to_k are live
+        if isinstance(num_past_obs, bool) or not isinstance(num_past_obs, int) or not 1 <= num_past_obs <= 8:
+            raise ValueError(f"num_past_obs = {num_past_obs}: 1 .. 8 conditioning tokens per sample")
+        self.num_past_obs = num_past_obs
         if not isinstance(gradient_checkpointing, bool):
             raise TypeError(f"gradient_checkpointing must be a bool, not {type(gradient_checkpointing).__name__}")
         # `--gradient_checkpointing` (train_svd.py:211-215, 628-629): every ResBlock and every transformer of `forward` keeps only
@@ -383,7 +389,10 @@ class UNetTrain:
 
     def concat(self, x1, x2):
         tape = self.tape
-        y = torch.cat([x1, x2], dim=1).contiguous()                        # a copy (plumbing)
+        # a level of fewer than 64 rows: a GEMM output carries pad rows up to 64 (zeros), a convolution output does not —
+        # the copy takes the rows both have, `Tape.add` gives each gradient its tensor's row count
+        rows = min(x1.shape[0], x2.shape[0])
+        y = torch.cat([x1[:rows], x2[:rows]], dim=1).contiguous()          # a copy (plumbing)
         C1 = x1.shape[1]
 
         def bwd():
@@ -522,6 +531,30 @@ class UNetTrain:
         v = self.linear(ehs16, q + ".attn2.to_v", 1, bias=False)
         return self.linear(v, q + ".attn2.to_out.0", 1, out_f32=True)
 
+    def cross_attention(self, q, h, ctx16, M, heads):
+        """The general cross-attention over P = num_past_obs tokens (attention.py:545-551 / 740-743): h + to_out(attn(norm2(h)
+        to_q, ctx to_k, ctx to_v)).  Every row of the sample shares the P keys (rows_per_item = M), spatial and temporal
+        block alike.  The softmax weights are not saved: the backward kernel recomputes them from Q and K."""
+        hip, tape = self.hip, self.tape
+        P, C = self.num_past_obs, heads * 64
+        Q = self.linear(self.layernorm(h, q + ".norm2", M), q + ".attn2.to_q", M, bias=False)
+        K = self.linear(ctx16, q + ".attn2.to_k", P, bias=False)              # rows padded to 64 by `linear`
+        V = self.linear(ctx16, q + ".attn2.to_v", P, bias=False)
+        Kp, Vp = K[:P].reshape(1, P, C), V[:P].reshape(1, P, C)
+        o = torch.empty(M, C, dtype=self.dt, device=self.device)
+        hip.cross_attn_fewkeys(Q, C, Kp, Vp, o, C, M, M, heads, P, 0.125)
+
+        def bwd():
+            do = tape.take(o, self.dt)
+            if do is None:
+                return
+            dQ, dK, dV = hip.cross_attn_fewkeys_backward(Q, C, Kp, Vp, do, C, M, M, heads, P, 0.125)
+            tape.add(Q, dQ)
+            tape.add(K, _pad_like(dK.reshape(P, C).to(self.dt), K))
+            tape.add(V, _pad_like(dV.reshape(P, C).to(self.dt), V))
+        tape.ops.append(bwd)
+        return self.linear(o, q + ".attn2.to_out.0", M, res=h)
+
     def ff(self, a, p, M, **epi):
         P = self.linear(a, p + ".net.0.proj", M)
         return self.linear(self.geglu(P, M), p + ".net.2", M, **epi)
@@ -534,7 +567,10 @@ class UNetTrain:
         h = self.linear(xn, p + ".proj_in", M)
         # spatial block (attention.py:462-582)
         o = self.self_attention(self.layernorm(h, b + ".norm1", M), b + ".attn1", M, T, S, heads)
-        h = self.linear(o, b + ".attn1.to_out.0", M, res=h, rowvec=self.cross_vector(b, ehs16), rows_per_vec=M)
+        if self.num_past_obs == 1:
+            h = self.linear(o, b + ".attn1.to_out.0", M, res=h, rowvec=self.cross_vector(b, ehs16), rows_per_vec=M)
+        else:
+            h = self.cross_attention(b, self.linear(o, b + ".attn1.to_out.0", M, res=h), ehs16, M, heads)
         feat = torch.from_numpy(sinusoid(np.arange(T), C)).to(self.device, self.dt)
         pos = self.mlp(_pad_rows(feat), p + ".time_pos_embed", T)                 # [T, C] frame-position embedding
         hs = self.ff(self.layernorm(h, b + ".norm3", M), b + ".ff", M, res=h)
@@ -542,7 +578,10 @@ class UNetTrain:
         hm0 = self._add_rowvec(hs, pos, S)
         hm = self.ff(self.layernorm(hm0, t + ".norm_in", M), t + ".ff_in", M, res=hm0)
         o = self.self_attention(self.layernorm(hm, t + ".norm1", M), t + ".attn1", M, 1, S, heads, temporal_T=T)
-        hm = self.linear(o, t + ".attn1.to_out.0", M, res=hm, rowvec=self.cross_vector(t, ehs16), rows_per_vec=M)
+        if self.num_past_obs == 1:
+            hm = self.linear(o, t + ".attn1.to_out.0", M, res=hm, rowvec=self.cross_vector(t, ehs16), rows_per_vec=M)
+        else:
+            hm = self.cross_attention(t, self.linear(o, t + ".attn1.to_out.0", M, res=hm), ehs16, M, heads)
         ht = self.ff(self.layernorm(hm, t + ".norm3", M), t + ".ff", M, res=hm)
         hb = self.blend(hs, ht, p + ".time_mixer")
         return self.linear(hb, p + ".proj_out", M, res=x)
@@ -573,8 +612,11 @@ class UNetTrain:
     # ------------------------------------------------------------------------------------------
     def forward(self, sample: torch.Tensor, timestep: float, ehs: torch.Tensor, added_time_ids: torch.Tensor,
                 action_ids: torch.Tensor) -> torch.Tensor:
-        """sample (1,T,8,h,w); ehs (1,1,Dctx); added_time_ids (1,3); action_ids (1,T,Ch).  Returns (1,T,4,h,w) fp32."""
+        """sample (1,T,8,h,w); ehs (1,num_past_obs,Dctx); added_time_ids (1,3); action_ids (1,T,Ch).  Returns (1,T,4,h,w) fp32."""
         cfg, hip, dev, dt = self.cfg, self.hip, self.device, self.dt
+        if ehs.numel() != self.num_past_obs * ehs.shape[-1]:
+            raise ValueError(f"ehs {tuple(ehs.shape)}: this tape was built for (1, {self.num_past_obs}, D) conditioning tokens "
+                             f"(num_past_obs = {self.num_past_obs})")
         if getattr(self, "tape", None) is not None:
             self.tape.release()                         # a forward without a backward (evaluation) leaves its tape behind
         self.tape, self.grads = Tape(hip), {}
@@ -597,7 +639,7 @@ class UNetTrain:
         emb_n = self.mlp(_pad_rows(n_feat), "add_embedding_noise", 1)
         emb = self.host_sum([emb_t, emb_a, emb_n], (T, E))
         emb_silu = self.silu(self.cast16(emb))                                     # [64, E], rows >= T are silu(0) = 0
-        ehs16 = _pad_rows(ehs.reshape(1, -1).to(dev, dt))
+        ehs16 = _pad_rows(ehs.reshape(self.num_past_obs, -1).to(dev, dt))
         # ---- conv_in
         x0 = torch.zeros(T * h * w, CIN_PAD, dtype=dt, device=dev)
         x0[:, :cin] = sample[0].permute(0, 2, 3, 1).reshape(-1, cin).to(dev, dt)
@@ -700,10 +742,11 @@ class UNetTrain32(UNetTrain):
 
 
 def make_unet_train(cfg: UNetConfig, state_dict: Dict[str, torch.Tensor], device="cuda:0", hip: Optional[Hip] = None,
-                    dtype: torch.dtype = torch.bfloat16, gradient_checkpointing: bool = False) -> UNetTrain:
+                    dtype: torch.dtype = torch.bfloat16, gradient_checkpointing: bool = False, num_past_obs: int = 1) -> UNetTrain:
     """The tape for `cfg`: `UNetTrain` up to 16 frames (unchanged behaviour for every existing user), `UNetTrain32` above."""
     cls = UNetTrain if cfg.num_frames <= TRAIN_MAX_FRAMES else UNetTrain32
-    return cls(cfg, state_dict, device, hip=hip, dtype=dtype, gradient_checkpointing=gradient_checkpointing)
+    return cls(cfg, state_dict, device, hip=hip, dtype=dtype, gradient_checkpointing=gradient_checkpointing,
+               num_past_obs=num_past_obs)
 
 
 class EMAShadow:
@@ -797,9 +840,12 @@ class Trainer:
                    "new+temp_layer": lambda n: ("temporal_transformer_block" in n) or ("action" in n) or ("noise" in n)}
 
     @staticmethod
-    def is_dead(name: str) -> bool:
+    def is_dead(name: str, num_past_obs: int = 1) -> bool:
         """Parameters that never receive a gradient under `micro_cond` (in the reference's autograd too: SURVEY.md 9.3): the
-        query / key side and the LayerNorm of the single-key cross-attentions, and `add_embedding` (overwritten, unet:458-482)."""
+        query / key side and the LayerNorm of the single-key cross-attentions, and `add_embedding` (overwritten, unet:458-482).
+        With num_past_obs > 1 the softmax over the tokens is not constant: only `add_embedding` stays dead."""
+        if num_past_obs > 1:
+            return name.startswith("add_embedding.")
         return ("attn2.to_q." in name or "attn2.to_k." in name or name.startswith("add_embedding.")
                 or ("transformer_blocks." in name and ".norm2." in name))
 
@@ -810,7 +856,8 @@ class Trainer:
         optimiser over ALL parameters would apply its decoupled weight decay to the frozen / dead ones on every step (and
         spend master / moment memory and collective bandwidth on 1.5 B parameters when only a few million train)."""
         want = cls.PARAM_TYPES[train_param_type]
-        return {k: tuple(v.shape) for k, v in net.master.items() if want(k) and not cls.is_dead(k)}
+        P = getattr(net, "num_past_obs", 1)
+        return {k: tuple(v.shape) for k, v in net.master.items() if want(k) and not cls.is_dead(k, P)}
 
     def __init__(self, net: "UNetTrain", lr: float = 1e-5, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2,
                  optimizer=None, loss_scale: Optional[float] = None, train_param_type: str = "full", grad_accum: int = 1,
@@ -982,7 +1029,8 @@ class Trainer:
         use_ema = (self.ema is not None) if use_ema is None else use_ema
         assert not use_ema or self.ema is not None, "validate(use_ema=True) needs Trainer(use_ema=True)"
         weights = self.ema.shadow if use_ema else self.net.master
-        unet = UNetHIP(self.net.cfg, weights, self.net.device, hip=self.net.hip, residual_fp32=residual_fp32)
+        unet = UNetHIP(self.net.cfg, weights, self.net.device, hip=self.net.hip, residual_fp32=residual_fp32,
+                       num_past_obs=getattr(self.net, "num_past_obs", 1))
         den = SVDDenoiser(unet, use_graph=False)
         se, n, psnrs, lat_psnrs = 0.0, 0, [], []
         for s in samples:

@@ -25,7 +25,13 @@ against `plain step + 1.15 x plain forward`; written to profiles/r25a_train_step
 `--num_past_obs P` (1 .. 8) measures the step of the served network on a PH x PW x 14 navigation clip with P conditioning tokens
 per sample (`UNetTrain(num_past_obs=P)`): forward / backward / step ms, peak GiB and, above 1, the summed ms of the 32
 cross-attentions — LayerNorm, to_q GEMM, forward kernel, backward kernels — with the backward's bytes/s against its minimum;
-written to profiles/r26a_train_step_ctx_P<P>_<size>x14_<dtype>.json."""
+written to profiles/r26a_train_step_ctx_P<P>_<size>x14_<dtype>.json.
+
+`--batch B` (with `--manip448` and / or `--frames N`, optionally `--gradient_checkpointing`) measures the step on batches of
+1, 2, 4, ... and B clips (`train.collate` of clips that differ in noise level, actions and tokens) on ONE tape in one process:
+per row ms per step, ms per clip, forward / backward ms, peak GiB, the kernel-family and GEMM-mode breakdown of one step, and
+the ratio of ms per clip to the B = 1 row of the same run — which is the unchanged single-clip path; written to
+profiles/r27a_train_step_batch_B<B>_<size>x<frames>_<dtype>[_ckpt].json."""
 import argparse
 import collections
 import dataclasses
@@ -375,6 +381,84 @@ def _probe_clip(Tn: int, manip448: bool):
     return cfg, (h, w), st
 
 
+def batch_probe(B: int, Tn: int, manip448: bool, dtype=torch.bfloat16, steps: int = 5, gradient_checkpointing: bool = False):
+    """`--batch B`: rows for 1, 2, 4, ... and B clips per step on one tape (module docstring)."""
+    import json
+    import statistics
+
+    from wiw_amd.train_unet import MAX_BATCH_ROWS, Trainer
+
+    cfg, (h, w), st1 = _probe_clip(Tn, manip448)
+    sizes = sorted({b for b in (1, 2, 4, 8, 16, 32, 64) if b < B} | {B})
+    if B > 1 and B * Tn * h * w > MAX_BATCH_ROWS:
+        raise SystemExit(f"--batch {B}: {B * Tn * h * w} rows, above MAX_BATCH_ROWS = {MAX_BATCH_ROWS}")
+    gen = torch.Generator().manual_seed(200)
+    clips = [st1]
+    for b in range(1, B):                                 # the same clip geometry; own latents, noise level, tokens and actions
+        lat, noise = torch.randn(1, Tn, 4, h, w, generator=gen) * 0.8, torch.randn(1, Tn, 4, h, w, generator=gen)
+        clips.append(T.prepare_step(lat, noise, 0.5 + 0.4 * b, torch.randn(1, 4, h, w, generator=gen),
+                                    torch.randn(1, 1, 1024, generator=gen), 0.02 + 0.01 * b, st1.action_ids.flip(1) if b % 2 else st1.action_ids))
+    net = make_unet_train(cfg, random_state_dict_torch(cfg, 0, dev, torch.float32), dev, dtype=dtype,
+                          gradient_checkpointing=gradient_checkpointing)
+    hip = net.hip
+    T.clear_wgrad_plans()
+    tr = Trainer(net, lr=1e-5, autotune=True)
+
+    def wall(fn):
+        torch.cuda.synchronize(); t0 = time.perf_counter()
+        out = fn()
+        torch.cuda.synchronize()
+        return 1e3 * (time.perf_counter() - t0), out
+
+    rows = []
+    for b in sizes:
+        st = T.collate(clips[:b])
+        for _ in range(2):                                # warm-up: this row count's weight-gradient plans, allocator
+            tr.step(st)
+        net.grads = {}
+        torch.cuda.synchronize()
+        torch.cuda.empty_cache()
+        torch.cuda.reset_peak_memory_stats()
+        fwd, bwd, whole = [], [], []
+        for _ in range(steps):
+            ms, pred = wall(lambda: net.forward(st.unet_input, st.timestep, st.ehs, st.added_time_ids, st.action_ids))
+            fwd.append(ms)
+            loss, dpred = T.TrainStep(hip).loss_and_grad(pred, st)
+            bwd.append(wall(lambda: net.backward(dpred.reshape(pred.shape), tr.loss_scale))[0])
+            del pred, dpred
+        for _ in range(steps):
+            whole.append(wall(lambda: tr.step(st))[0])
+        peak = torch.cuda.max_memory_allocated() / 2 ** 30
+        hip.kernel_profile, hip.gemm_profile = [], []
+        ms_prof, _ = wall(lambda: tr.step(st))
+        fam, gm = collections.defaultdict(lambda: [0, 0.0]), collections.defaultdict(lambda: [0, 0.0])
+        for e0, e1, family, _, _ in hip.kernel_profile:
+            fam[family][0] += 1; fam[family][1] += e0.elapsed_time(e1)
+        for e0, e1, _, mode, _ in hip.gemm_profile:
+            gm[f"gemm mode {mode}"][0] += 1; gm[f"gemm mode {mode}"][1] += e0.elapsed_time(e1)
+        hip.kernel_profile = hip.gemm_profile = None
+        step_ms = statistics.median(whole)
+        table = lambda d: {k: {"calls": n, "ms": round(ms, 3), "ms_per_clip": round(ms / b, 3)}  # noqa: E731
+                           for k, (n, ms) in sorted(d.items(), key=lambda kv: -kv[1][1])}
+        rows.append({"batch": b, "rows_level0": b * Tn * h * w, "step_ms": round(step_ms, 2), "ms_per_clip": round(step_ms / b, 2),
+                     "step_ms_all": [round(x, 1) for x in whole], "forward_ms": round(statistics.median(fwd), 2),
+                     "backward_ms": round(statistics.median(bwd), 2), "peak_GiB": round(peak, 2),
+                     "sample_losses": [round(x, 4) for x in tr.last_sample_losses], "step_ms_with_events": round(ms_prof, 1),
+                     "kernel_families": table(fam), "gemms": table(gm)})
+        rows[-1]["ms_per_clip_over_B1"] = round(rows[-1]["ms_per_clip"] / rows[0]["ms_per_clip"], 4)
+        print(json.dumps({k: v for k, v in rows[-1].items() if k not in ("kernel_families", "gemms")}), flush=True)
+    rec = {"probe": "train_step_batch", "size": f"{8 * h}x{8 * w}x{Tn}", "latent": [h, w], "dtype": str(dtype), "tape": type(net).__name__,
+           "task": cfg.task_type, "gradient_checkpointing": gradient_checkpointing, "steps_per_row": steps, "loss_scale": tr.loss_scale,
+           "wgrad_plans": len(T.wgrad_plans()), "rows": rows}
+    print(json.dumps(rec))
+    out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
+                       f"r27a_train_step_batch_B{B}_{8 * h}x{8 * w}x{Tn}_{'fp16' if dtype == torch.float16 else 'bf16'}"
+                       f"{'_ckpt' if gradient_checkpointing else ''}.json")
+    with open(out, "w") as f:
+        json.dump(rec, f, indent=1)
+        f.write("\n")
+
+
 def checkpoint_cost(Tn: int, manip448: bool, dtype=torch.bfloat16, steps: int = 5):
     """Activation checkpointing off / on / off / on on ONE tape (the keyword is configuration: `forward` reads it)."""
     import json
@@ -572,11 +656,20 @@ if __name__ == "__main__":
     ap.add_argument("--num_past_obs", type=int, default=None, help="time the fine-tuning step (PH x PW x 14 navigation) with this many "
                     "conditioning tokens per sample (1 .. 8) and, above 1, the 32 cross-attentions by piece; written to "
                     "profiles/r26a_train_step_ctx_P<P>_<size>x14_<dtype>.json")
+    ap.add_argument("--batch", type=int, default=None, help="with --manip448 / --frames: the step on batches of 1, 2, 4, ... and "
+                    "this many clips on one tape (ms per step, ms per clip, peak GiB, ratio to the B = 1 row; with "
+                    "--gradient_checkpointing: under activation checkpointing); written to profiles/r27a_train_step_batch_*.json")
     ap.add_argument("--steps", type=int, default=5, help="--max_grad_norm / --manip448 / --frames / --num_past_obs: timed steps per block")
     ap.add_argument("--dtype", choices=["bf16", "fp16"], default="bf16")
     args = ap.parse_args()
     if args.num_past_obs is not None:
         past_obs_probe(args.num_past_obs, torch.float16 if args.dtype == "fp16" else torch.bfloat16, args.steps)
+        sys.exit(0)
+    if args.batch is not None:
+        if not 1 <= args.batch <= 64:
+            ap.error("--batch: 1 .. 64 clips per step")
+        batch_probe(args.batch, 14 if args.frames is None else args.frames, args.manip448,
+                    torch.float16 if args.dtype == "fp16" else torch.bfloat16, args.steps, args.gradient_checkpointing)
         sys.exit(0)
     if args.gradient_checkpointing:
         if not (args.manip448 or args.frames is not None):

@@ -222,16 +222,23 @@ EXPORTS_CROSS_TRAIN = {
                                                   C.c_int, C.c_float]),
 }
 
+# include/wiw_train_batch.h: the batched entry point of the fine-tuning step (several clips per step), bound on the same two
+# libraries
+EXPORTS_TRAIN_BATCH = {
+    "wiw_edm_loss_grad_batched": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p,
+                                            C.c_void_p, C.c_void_p, C.c_int]),
+}
+
 
 def load_library(path: str = LIB_PATH) -> C.CDLL:
-    """dlopen the C-ABI library and declare every prototype of include/wiw_svd.h and include/wiw_cross_attn_train.h.  Raises if
-    absent."""
+    """dlopen the C-ABI library and declare every prototype of include/wiw_svd.h, include/wiw_cross_attn_train.h and
+    include/wiw_train_batch.h.  Raises if absent."""
     if not os.path.exists(path):
         raise RuntimeError(
             f"{path} not found: the HIP extension is required (build it with "
             f"`python world-in-world_amd/build.py`); there is no CPU or PyTorch fallback")
     lib = C.CDLL(path)
-    for name, (res, args) in (*EXPORTS.items(), *EXPORTS_CROSS_TRAIN.items()):
+    for name, (res, args) in (*EXPORTS.items(), *EXPORTS_CROSS_TRAIN.items(), *EXPORTS_TRAIN_BATCH.items()):
         fn = getattr(lib, name)  # AttributeError if the symbol is missing
         fn.restype = res
         fn.argtypes = args
@@ -815,6 +822,22 @@ class Hip:
         self._ck(self.lib.wiw_edm_loss_grad(self._stream(), _p(pred), _p(noisy), _p(target), n, float(sigma), _p(grad),
                                             _p(partial), nb), "wiw_edm_loss_grad")
         return partial.sum() / n, grad
+
+    def edm_loss_grad_batched(self, pred, noisy, target, sigmas):
+        """EDM loss of B samples (fp32 tensors (B, ...) of equal shape; sigmas: B floats, or a tensor of B) and the gradient of
+        their MEAN loss w.r.t. `pred` (csrc/train_batch.hip): returns (per-sample losses (B,) device tensor, grad).  Sample b's
+        partial sums are those `edm_loss_grad` makes for it alone; the gradient is the single-sample one times fp32(1 / B)."""
+        B = pred.shape[0]
+        n = pred.numel() // B
+        assert pred.is_contiguous() and noisy.is_contiguous() and target.is_contiguous() and noisy.shape == target.shape == pred.shape
+        sig = torch.as_tensor(sigmas, dtype=torch.float32).reshape(-1).to(self.device)
+        assert sig.numel() == B, f"edm_loss_grad_batched: {sig.numel()} sigmas for {B} samples"
+        grad = torch.empty_like(pred)
+        nb = min(1024, (n + 255) // 256)
+        partial = torch.empty(B, nb, dtype=torch.float32, device=self.device)
+        self._ck(self.lib.wiw_edm_loss_grad_batched(self._stream(), _p(pred), _p(noisy), _p(target), n, B, _p(sig), _p(grad),
+                                                    _p(partial), nb), "wiw_edm_loss_grad_batched")
+        return partial.sum(1) / n, grad
 
     # ---- backward building blocks (row f2; csrc/train.hip)
     def colsum(self, X, rows, Cn, parts=None, units=1):

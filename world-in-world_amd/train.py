@@ -42,23 +42,82 @@ def apply_conditioning_dropout(ehs: torch.Tensor, cond_latents: torch.Tensor, ac
 
 @dataclass
 class StepInputs:
-    """What one step feeds the UNet and the loss (one sample per GPU, as the reference: train_svd.py:877)."""
-    unet_input: torch.Tensor      # (1,T,8,h,w) fp32: noisy / sqrt(sigma^2 + 1) | conditioning latents
-    timestep: float               # 0.25 ln sigma
-    noisy: torch.Tensor           # (1,T,4,h,w)
+    """What one step feeds the UNet and the loss: B independent samples (`--per_gpu_batch_size B`, train_svd.py:946-951: the
+    loss is the mean over the samples of their mean weighted squared errors).  B = 1 is the reference's own setting (:877) and
+    keeps Python floats for `sigma` / `timestep`; for B > 1 they are 1-D fp32 tensors of B and every tensor leads with B.
+    Every sample carries its OWN sigma, timestep, noise_aug_strength, action ids, conditioning tokens and dropout draw — where
+    the reference's loop at bsz > 1 feeds `cond_sigmas[0]` to all samples (:869, "TODO: support batch > 1") and squeezes the
+    batch axis of `past_obs` (:890)."""
+    unet_input: torch.Tensor      # (B,T,8,h,w) fp32: noisy / sqrt(sigma^2 + 1) | conditioning latents
+    timestep: object              # 0.25 ln sigma: float (B = 1) | fp32 tensor (B,)
+    noisy: torch.Tensor           # (B,T,4,h,w)
     target: torch.Tensor          # the clean latents
-    sigma: float
-    added_time_ids: torch.Tensor  # (1,3) = (7, 127, noise_aug_strength)
-    ehs: torch.Tensor
-    action_ids: torch.Tensor
+    sigma: object                 # float (B = 1) | fp32 tensor (B,)
+    added_time_ids: torch.Tensor  # (B,3) = (7, 127, noise_aug_strength)
+    ehs: torch.Tensor             # (B,P,D)
+    action_ids: torch.Tensor      # (B,T,Ch)
+
+    @property
+    def batch(self) -> int:
+        return int(self.unet_input.shape[0])
 
 
-def prepare_step(latents: torch.Tensor, noise: torch.Tensor, sigma: float, cond_latents: torch.Tensor, ehs: torch.Tensor,
-                 noise_aug_strength: float, action_ids: torch.Tensor, dropout_prob: Optional[float] = None,
+def _per_sample(v, B: int, what: str) -> list:
+    """A float, or a sequence / tensor of B floats -> B Python floats."""
+    if isinstance(v, torch.Tensor):
+        v = v.reshape(-1).tolist()
+    vs = [float(x) for x in v] if isinstance(v, (list, tuple)) or hasattr(v, "__len__") else [float(v)] * B
+    if len(vs) != B:
+        raise ValueError(f"{what}: {len(vs)} values for a batch of {B} samples")
+    return vs
+
+
+def collate(steps) -> StepInputs:
+    """Stack `StepInputs` of equal shape and equal token count P into one batch, in order.  A single B = 1 element comes back as
+    it is (floats and all); otherwise `sigma` / `timestep` become fp32 tensors of B.  Mixed shapes: ValueError (variable shapes
+    inside a batch are not supported)."""
+    steps = list(steps)
+    if not steps:
+        raise ValueError("collate: no samples")
+    if len(steps) == 1:
+        return steps[0]
+    first = steps[0]
+    for i, st in enumerate(steps[1:], 1):
+        for f in ("unet_input", "noisy", "target", "added_time_ids", "ehs", "action_ids"):
+            a, b = getattr(first, f), getattr(st, f)
+            if tuple(a.shape[1:]) != tuple(b.shape[1:]) or a.dtype != b.dtype:
+                raise ValueError(f"collate: sample {i} has {f} {tuple(b.shape)} {b.dtype}, sample 0 {tuple(a.shape)} {a.dtype}: "
+                                 f"the samples of a batch share one shape (and one number of conditioning tokens)")
+    cat = lambda f: torch.cat([getattr(st, f) for st in steps], dim=0)  # noqa: E731
+    vec = lambda f: torch.tensor([x for st in steps for x in _per_sample(getattr(st, f), st.batch, f)], dtype=torch.float32)  # noqa: E731
+    return StepInputs(cat("unet_input"), vec("timestep"), cat("noisy"), cat("target"), vec("sigma"), cat("added_time_ids"), cat("ehs"),
+                      cat("action_ids"))
+
+
+def prepare_step(latents: torch.Tensor, noise: torch.Tensor, sigma, cond_latents: torch.Tensor, ehs: torch.Tensor,
+                 noise_aug_strength, action_ids: torch.Tensor, dropout_prob: Optional[float] = None,
                  random_p: Optional[torch.Tensor] = None) -> StepInputs:
-    """train_svd.py:888-931 for one sample: noisy = latents + sigma noise; input = noisy / sqrt(sigma^2 + 1) concatenated
-    with the (possibly dropped) conditioning latents on the channel axis; t = 0.25 ln sigma."""
-    assert latents.shape[0] == 1 and latents.shape == noise.shape
+    """train_svd.py:888-931: noisy = latents + sigma noise; input = noisy / sqrt(sigma^2 + 1) concatenated with the (possibly
+    dropped) conditioning latents on the channel axis; t = 0.25 ln sigma.  latents (B, T, 4, h, w); `sigma` and
+    `noise_aug_strength` floats, or sequences of B (one per sample); `random_p` (B,).  B > 1 is, by construction, `collate` of
+    the B single-sample calls: sample b sees its own sigma, noise_aug_strength and dropout draw (the reference's loop hands
+    `cond_sigmas[0]` to every sample, :869)."""
+    assert latents.shape == noise.shape
+    B = latents.shape[0]
+    if B > 1:
+        sig, aug = _per_sample(sigma, B, "sigma"), _per_sample(noise_aug_strength, B, "noise_aug_strength")
+        for name, t in (("cond_latents", cond_latents), ("ehs", ehs), ("action_ids", action_ids)):
+            if t.shape[0] != B:
+                raise ValueError(f"prepare_step: {name} {tuple(t.shape)} for a batch of {B} samples")
+        if random_p is not None and random_p.reshape(-1).shape[0] != B:
+            raise ValueError(f"prepare_step: random_p {tuple(random_p.shape)} for a batch of {B} samples")
+        rp = None if random_p is None else random_p.reshape(-1)
+        return collate([prepare_step(latents[b:b + 1], noise[b:b + 1], sig[b], cond_latents[b:b + 1], ehs[b:b + 1], aug[b],
+                                     action_ids[b:b + 1], dropout_prob, None if rp is None else rp[b:b + 1]) for b in range(B)])
+    if not isinstance(sigma, (int, float)):
+        sigma = _per_sample(sigma, 1, "sigma")[0]
+    if not isinstance(noise_aug_strength, (int, float)):
+        noise_aug_strength = _per_sample(noise_aug_strength, 1, "noise_aug_strength")[0]
     ehs, cond_latents, action_ids = apply_conditioning_dropout(ehs, cond_latents, action_ids, dropout_prob, random_p)
     noisy = latents + noise * sigma
     inp = torch.cat([noisy / (sigma ** 2 + 1) ** 0.5, cond_latents.unsqueeze(1).repeat(1, latents.shape[1], 1, 1, 1)], dim=2)
@@ -69,8 +128,8 @@ def prepare_step(latents: torch.Tensor, noise: torch.Tensor, sigma: float, cond_
 @torch.no_grad()
 def batch_from_pixels(front, pixel_values: torch.Tensor, past_obs: torch.Tensor, actions, *, scaling_factor: Optional[float] = None,
                       dropout_prob: Optional[float] = None, generator: Optional[torch.Generator] = None,
-                      draws: Optional[dict] = None, action_input_channel: int = 10) -> StepInputs:
-    """One training sample from PIXELS, as the reference's loop builds it (train_svd.py:846-931), on the HIP front end:
+                      draws=None, action_input_channel: int = 10) -> StepInputs:
+    """Training samples from PIXELS, as the reference's loop builds them (train_svd.py:846-931), on the HIP front end:
         latents      = vae.encode(frames).latent_dist.sample() * scaling_factor            (:86-95, :856)
         noise        = sample_latent_noise(actions, ...)                                    (:873; pipeline:750-786)
         cond_sigma   = rand_log_normal(-3.0, 0.5); cond image = frame 0 + randn * cond_sigma   (:876-880)
@@ -83,15 +142,33 @@ def batch_from_pixels(front, pixel_values: torch.Tensor, past_obs: torch.Tensor,
     manipulation rows [x, y, z, qx, qy, qz, qw, gripper]: `manip_action_ids` (10 channels; their positional form when the
     network's `action_input_channel` is T + 9) and NO noise rotation (the reference's `sample_latent_noise(..., args.task_type)`
     rotates the panorama for navigation only).  `draws` overrides the random draws (tests / replay): vae_eps (T, L, h, w), cond_eps
-    (1, L, h, w), pixel_noise (1, 3, H, W), latent_noise (1, T, L, h, w), sigma, cond_sigma (floats), random_p ((1,))."""
+    (1, L, h, w), pixel_noise (1, 3, H, W), latent_noise (1, T, L, h, w), sigma, cond_sigma (floats), random_p ((1,)).
+    A loader batch — pixel_values (B, T, 3, H, W), past_obs (B, P, 3, H', W'), actions (B, T) or (B, T, 8) — gives the batched
+    `StepInputs`: by definition `collate` of the B single-sample calls made IN ORDER on the same `generator` (all of sample 0's
+    draws — vae_eps, latent_noise, cond_sigma, pixel_noise, cond_eps, sigma, random_p, in that order — then all of sample 1's,
+    ...), so a batch replays as B single clips.  Every sample gets its own cond_sigma (the reference's loop uses
+    `cond_sigmas[0]` for all of them, train_svd.py:869) and its own P tokens (the reference squeezes the batch axis of
+    `past_obs`, :890).  `draws` for B > 1: a list of B dicts."""
     import numpy as np
+
+    if pixel_values.dim() == 5 and pixel_values.shape[0] > 1:
+        B = pixel_values.shape[0]
+        acts_b = np.asarray(actions)
+        if past_obs.shape[0] != B or acts_b.shape[0] != B:
+            raise ValueError(f"batch_from_pixels: pixel_values has {B} samples, past_obs {past_obs.shape[0]}, actions {acts_b.shape[0]}")
+        if draws is not None and (isinstance(draws, dict) or len(draws) != B):
+            raise ValueError(f"batch_from_pixels: `draws` of a batch of {B} samples is a list of {B} dicts")
+        return collate([batch_from_pixels(front, pixel_values[b:b + 1], past_obs[b:b + 1], acts_b[b:b + 1],
+                                          scaling_factor=scaling_factor, dropout_prob=dropout_prob, generator=generator,
+                                          draws=None if draws is None else draws[b], action_input_channel=action_input_channel)
+                        for b in range(B)])
 
     from .pipeline import action_encode_positional, action_ids_idx_encode, manip_action_ids, rotate_latent_noise
 
     d = dict(draws or {})
     vae = front.vae
     sf = float(vae.scaling_factor if scaling_factor is None else scaling_factor)
-    assert pixel_values.dim() == 5 and pixel_values.shape[0] == 1, "one sample per step, as the reference (train_svd.py:877)"
+    assert pixel_values.dim() == 5 and pixel_values.shape[0] == 1
     T = pixel_values.shape[1]
     dev = vae.device
     px = pixel_values[0].to(dev, torch.float32)
@@ -434,9 +511,12 @@ class TrainStep:
         self.hip = hip
 
     def loss_and_grad(self, model_pred: torch.Tensor, step: StepInputs) -> Tuple[torch.Tensor, torch.Tensor]:
-        """EDM loss (train_svd.py:940-952) and dL/d(model_pred), fp32, on the device."""
+        """EDM loss (train_svd.py:940-952) and dL/d(model_pred), fp32, on the device.  One sample: (0-d loss, grad) from
+        `wiw_edm_loss_grad`.  B > 1: (per-sample losses (B,), gradient of their MEAN) from `wiw_edm_loss_grad_batched`."""
         dev = self.hip.device
         f = lambda t: t.to(dev, torch.float32).contiguous()  # noqa: E731
+        if model_pred.shape[0] > 1:
+            return self.hip.edm_loss_grad_batched(f(model_pred), f(step.noisy), f(step.target), step.sigma)
         return self.hip.edm_loss_grad(f(model_pred), f(step.noisy), f(step.target), step.sigma)
 
     def backward(self, *_a, **_k):

@@ -1,7 +1,7 @@
 """Training graph of the action-conditioned SVD UNet on the HIP kernels — SURVEY.md 8(f) row 2 (`FTsvd/train_svd.py:844-970`).
 
-`UNetTrain.forward` evaluates `UNetSpatioTemporalConditionModel.forward` (unet:402-575, micro_cond, one sample per GPU as the
-reference's loop) in the UN-FUSED order training needs and records every operator on a tape; `backward` replays the tape in
+`UNetTrain.forward` evaluates `UNetSpatioTemporalConditionModel.forward` (unet:402-575, micro_cond; one sample per GPU as the
+reference's loop, or a batch of B independent samples with rows (b, t, s)) in the UN-FUSED order training needs and records every operator on a tape; `backward` replays the tape in
 reverse with the backward building blocks of `train.py` / `csrc/train.hip` and returns fp32 gradients of every live parameter in
 the reference's state-dict layout.  The exactly dead parameters of the inference path (single-key cross-attention `norm2`,
 `attn2.to_q/to_k`; `add_embedding`) are dead here too and get no gradient — as in the reference's autograd.
@@ -117,6 +117,10 @@ def _pad_rows(t: torch.Tensor, mult: int = 64) -> torch.Tensor:
 
 
 TRAIN_MAX_FRAMES = 16   # `self_attention` pads the temporal sequences to Tp = 16 rows
+# B > 1: first-level rows B T h w of `forward` up to those of ONE 32-frame 576 x 1024 clip, the most this tape has been run at.
+# The training-only kernels (csrc/train.hip, csrc/cross_attn_bwd.hip) address rows x leading dimension in 64 bits; nothing
+# below this bound sets a lower one
+MAX_BATCH_ROWS = 32 * 72 * 128
 
 
 def attn_padded_rows(S: int) -> int:
@@ -476,18 +480,25 @@ class UNetTrain:
         h = self.linear(x, p + ".linear_1", M)                 # rows padded to 64 by `linear`
         return self.linear(self.silu(h), p + ".linear_2", M, out_f32=out_f32)
 
-    def host_sum(self, terms, shape):
-        """fp32 sum of small [T, E] tensors with broadcasting rows (the three embeddings of unet:465-487); plumbing."""
+    def host_sum(self, terms, shape, groups=1):
+        """fp32 sum of small [T, E] tensors with broadcasting rows (the three embeddings of unet:465-487); plumbing.
+        groups = B > 1: `shape` is [B T, E]; a term of B rows is per sample — row b goes to the T rows of sample b and its
+        gradient is their sum."""
         tape = self.tape
+        per = shape[0] // groups
+        spread = lambda t: groups > 1 and per > 1 and t.shape[0] == groups  # noqa: E731
         y = torch.zeros(shape, dtype=torch.float32, device=self.device)
         for t in terms:
-            y = y + t.float()
+            y = y + (t.float().repeat_interleave(per, dim=0) if spread(t) else t.float())
 
         def bwd():
             dy = tape.take(y)
             if dy is None:
                 return
             for t in terms:
+                if spread(t):
+                    tape.add(t, dy.float().reshape(groups, per, -1).sum(1))
+                    continue
                 tape.add(t, dy.float().sum(0, keepdim=True) if t.shape[0] == 1 and shape[0] > 1 else dy.float())
         tape.ops.append(bwd)
         return y
@@ -509,16 +520,17 @@ class UNetTrain:
     # blocks
     # ------------------------------------------------------------------------------------------
     def res_block(self, p, x, Cin, Cout, M, H, W, T, emb_silu, eps):
-        """SpatioTemporalResBlock (resnet.py:686-716)."""
+        """SpatioTemporalResBlock (resnet.py:686-716).  Rows (b, t, s): the spatial GroupNorm has B T units of S rows, the temporal
+        one B units of T S rows; the temporal convolutions take T, so a clip never reads its neighbour's frames."""
         S = H * W
         s, t = p + ".spatial_res_block", p + ".temporal_res_block"
-        te_s = self.linear(emb_silu, s + ".time_emb_proj", T, out_f32=True)          # [T, Cout] per-frame vectors
+        te_s = self.linear(emb_silu, s + ".time_emb_proj", self.B * T, out_f32=True)  # [B T, Cout] per-frame vectors
         h = self.groupnorm(x, s + ".norm1", M, S, eps, True)
         h = self.conv(h, s + ".conv1", M, H, W, rowvec=te_s, rows_per_vec=S)
         h = self.groupnorm(h, s + ".norm2", M, S, eps, True)
         sc = self.conv1x1(x, s + ".conv_shortcut", M) if (s + ".conv_shortcut.weight") in self.master else x
         xs = self.conv(h, s + ".conv2", M, H, W, res=sc)
-        te_t = self.linear(emb_silu, t + ".time_emb_proj", T, out_f32=True)
+        te_t = self.linear(emb_silu, t + ".time_emb_proj", self.B * T, out_f32=True)
         h = self.groupnorm(xs, t + ".norm1", M, T * S, eps, True)
         h = self.conv(h, t + ".conv1", M, H, W, mode=A_CONV_T3, T=T, rowvec=te_t, rows_per_vec=S)
         h = self.groupnorm(h, t + ".norm2", M, T * S, eps, True)
@@ -527,31 +539,31 @@ class UNetTrain:
 
     def cross_vector(self, q, ehs16):
         """Single-key cross-attention: softmax over one key == 1, so attn2(x) = to_out(to_v(ctx)), one [1, C]
-        vector; norm2 / to_q / to_k receive no gradient."""
-        v = self.linear(ehs16, q + ".attn2.to_v", 1, bias=False)
-        return self.linear(v, q + ".attn2.to_out.0", 1, out_f32=True)
+        vector per sample (B rows, applied with rows_per_vec = M / B); norm2 / to_q / to_k receive no gradient."""
+        v = self.linear(ehs16, q + ".attn2.to_v", self.B, bias=False)
+        return self.linear(v, q + ".attn2.to_out.0", self.B, out_f32=True)
 
     def cross_attention(self, q, h, ctx16, M, heads):
         """The general cross-attention over P = num_past_obs tokens (attention.py:545-551 / 740-743): h + to_out(attn(norm2(h)
-        to_q, ctx to_k, ctx to_v)).  Every row of the sample shares the P keys (rows_per_item = M), spatial and temporal
+        to_q, ctx to_k, ctx to_v)).  Every row of a sample shares its P keys (rows_per_item = M / B), spatial and temporal
         block alike.  The softmax weights are not saved: the backward kernel recomputes them from Q and K."""
         hip, tape = self.hip, self.tape
-        P, C = self.num_past_obs, heads * 64
+        P, C, B = self.num_past_obs, heads * 64, self.B
         Q = self.linear(self.layernorm(h, q + ".norm2", M), q + ".attn2.to_q", M, bias=False)
-        K = self.linear(ctx16, q + ".attn2.to_k", P, bias=False)              # rows padded to 64 by `linear`
-        V = self.linear(ctx16, q + ".attn2.to_v", P, bias=False)
-        Kp, Vp = K[:P].reshape(1, P, C), V[:P].reshape(1, P, C)
+        K = self.linear(ctx16, q + ".attn2.to_k", B * P, bias=False)          # rows padded to 64 by `linear`
+        V = self.linear(ctx16, q + ".attn2.to_v", B * P, bias=False)
+        Kp, Vp = K[:B * P].reshape(B, P, C), V[:B * P].reshape(B, P, C)
         o = torch.empty(M, C, dtype=self.dt, device=self.device)
-        hip.cross_attn_fewkeys(Q, C, Kp, Vp, o, C, M, M, heads, P, 0.125)
+        hip.cross_attn_fewkeys(Q, C, Kp, Vp, o, C, M, M // B, heads, P, 0.125)
 
         def bwd():
             do = tape.take(o, self.dt)
             if do is None:
                 return
-            dQ, dK, dV = hip.cross_attn_fewkeys_backward(Q, C, Kp, Vp, do, C, M, M, heads, P, 0.125)
+            dQ, dK, dV = hip.cross_attn_fewkeys_backward(Q, C, Kp, Vp, do, C, M, M // B, heads, P, 0.125)
             tape.add(Q, dQ)
-            tape.add(K, _pad_like(dK.reshape(P, C).to(self.dt), K))
-            tape.add(V, _pad_like(dV.reshape(P, C).to(self.dt), V))
+            tape.add(K, _pad_like(dK.reshape(B * P, C).to(self.dt), K))
+            tape.add(V, _pad_like(dV.reshape(B * P, C).to(self.dt), V))
         tape.ops.append(bwd)
         return self.linear(o, q + ".attn2.to_out.0", M, res=h)
 
@@ -560,43 +572,48 @@ class UNetTrain:
         return self.linear(self.geglu(P, M), p + ".net.2", M, **epi)
 
     def transformer(self, p, x, C, M, H, W, T, heads, ehs16):
-        """TransformerSpatioTemporalModel (transformer_temporal.py:279-382), one layer, one sample."""
-        S = H * W
+        """TransformerSpatioTemporalModel (transformer_temporal.py:279-382), one layer.  Rows (b, t, s): B T spatial sequences of S
+        tokens, B S temporal ones of T frames; the frame-position embedding repeats per sample."""
+        S, B = H * W, self.B
         b, t = p + ".transformer_blocks.0", p + ".temporal_transformer_blocks.0"
         xn = self.groupnorm(x, p + ".norm", M, S, 1e-6, False)
         h = self.linear(xn, p + ".proj_in", M)
         # spatial block (attention.py:462-582)
-        o = self.self_attention(self.layernorm(h, b + ".norm1", M), b + ".attn1", M, T, S, heads)
+        o = self.self_attention(self.layernorm(h, b + ".norm1", M), b + ".attn1", M, B * T, S, heads)
         if self.num_past_obs == 1:
-            h = self.linear(o, b + ".attn1.to_out.0", M, res=h, rowvec=self.cross_vector(b, ehs16), rows_per_vec=M)
+            h = self.linear(o, b + ".attn1.to_out.0", M, res=h, rowvec=self.cross_vector(b, ehs16), rows_per_vec=M // B)
         else:
             h = self.cross_attention(b, self.linear(o, b + ".attn1.to_out.0", M, res=h), ehs16, M, heads)
         feat = torch.from_numpy(sinusoid(np.arange(T), C)).to(self.device, self.dt)
         pos = self.mlp(_pad_rows(feat), p + ".time_pos_embed", T)                 # [T, C] frame-position embedding
         hs = self.ff(self.layernorm(h, b + ".norm3", M), b + ".ff", M, res=h)
         # temporal block on hs + emb (attention.py:707-762); rows stay (t, s): every operator but the attention is per token
-        hm0 = self._add_rowvec(hs, pos, S)
+        hm0 = self._add_rowvec(hs, pos, S, repeat=B)
         hm = self.ff(self.layernorm(hm0, t + ".norm_in", M), t + ".ff_in", M, res=hm0)
-        o = self.self_attention(self.layernorm(hm, t + ".norm1", M), t + ".attn1", M, 1, S, heads, temporal_T=T)
+        o = self.self_attention(self.layernorm(hm, t + ".norm1", M), t + ".attn1", M, B, S, heads, temporal_T=T)
         if self.num_past_obs == 1:
-            hm = self.linear(o, t + ".attn1.to_out.0", M, res=hm, rowvec=self.cross_vector(t, ehs16), rows_per_vec=M)
+            hm = self.linear(o, t + ".attn1.to_out.0", M, res=hm, rowvec=self.cross_vector(t, ehs16), rows_per_vec=M // B)
         else:
             hm = self.cross_attention(t, self.linear(o, t + ".attn1.to_out.0", M, res=hm), ehs16, M, heads)
         ht = self.ff(self.layernorm(hm, t + ".norm3", M), t + ".ff", M, res=hm)
         hb = self.blend(hs, ht, p + ".time_mixer")
         return self.linear(hb, p + ".proj_out", M, res=x)
 
-    def _add_rowvec(self, x, vec, rows_per_vec):
-        """x + vec[row // rows_per_vec] (vec fp32 [units, C]): a 1x... broadcast add through the GEMM-free path."""
+    def _add_rowvec(self, x, vec, rows_per_vec, repeat=1):
+        """x + vec[(row // rows_per_vec) % units] (vec fp32 [units, C]): a 1x... broadcast add through the GEMM-free path.
+        repeat = B: the units repeat per sample; the gradient of vec is the sum over samples of the per-(b, unit) column sums."""
         hip, tape = self.hip, self.tape
         rep = vec.to(self.dt).repeat_interleave(rows_per_vec, dim=0).contiguous()      # plumbing: broadcast copy
+        if repeat > 1:
+            rep = rep.repeat(repeat, 1)
         y = hip.axpby(x[: rep.shape[0]], 1.0, rep, 1.0)                                 # (x may carry pad rows: M < 64)
 
         def bwd():
             dy = tape.take(y, self.dt)
             if dy is not None:
                 tape.add(x, dy)
-                tape.add(vec, self._unit_colsum(dy, vec.shape[0], rows_per_vec))
+                cs = self._unit_colsum(dy, repeat * vec.shape[0], rows_per_vec)
+                tape.add(vec, cs if repeat == 1 else cs.reshape(repeat, vec.shape[0], -1).sum(0))
         tape.ops.append(bwd)
         return y
 
@@ -610,41 +627,70 @@ class UNetTrain:
     # ------------------------------------------------------------------------------------------
     # the network
     # ------------------------------------------------------------------------------------------
-    def forward(self, sample: torch.Tensor, timestep: float, ehs: torch.Tensor, added_time_ids: torch.Tensor,
-                action_ids: torch.Tensor) -> torch.Tensor:
-        """sample (1,T,8,h,w); ehs (1,num_past_obs,Dctx); added_time_ids (1,3); action_ids (1,T,Ch).  Returns (1,T,4,h,w) fp32."""
-        cfg, hip, dev, dt = self.cfg, self.hip, self.device, self.dt
-        if ehs.numel() != self.num_past_obs * ehs.shape[-1]:
-            raise ValueError(f"ehs {tuple(ehs.shape)}: this tape was built for (1, {self.num_past_obs}, D) conditioning tokens "
+    def _check_batch(self, sample, timestep, ehs, added_time_ids, action_ids):
+        """B of `forward`'s arguments, checked before anything is launched; -> (B, the B timesteps)."""
+        if sample.dim() != 5:
+            raise ValueError(f"sample {tuple(sample.shape)}: (B, T, 8, h, w)")
+        B = int(sample.shape[0])
+        if B > 1:
+            for name, t in (("ehs", ehs), ("added_time_ids", added_time_ids), ("action_ids", action_ids)):
+                if t.dim() < 2 or t.shape[0] != B:
+                    raise ValueError(f"{name} {tuple(t.shape)}: sample {tuple(sample.shape)} is a batch of {B} — every argument "
+                                     f"leads with the same B")
+            if isinstance(timestep, (int, float)):
+                raise ValueError(f"timestep {timestep!r}: a batch of {B} samples takes {B} timesteps (one 0.25 ln sigma per sample)")
+        ts = [float(x) for x in torch.as_tensor(timestep, dtype=torch.float32).reshape(-1).tolist()] if B > 1 else [timestep]
+        if len(ts) != B:
+            raise ValueError(f"timestep: {len(ts)} values for a batch of {B} samples")
+        if ehs.numel() != B * self.num_past_obs * ehs.shape[-1]:
+            raise ValueError(f"ehs {tuple(ehs.shape)}: this tape was built for ({B}, {self.num_past_obs}, D) conditioning tokens "
                              f"(num_past_obs = {self.num_past_obs})")
+        rows = B * sample.shape[1] * sample.shape[3] * sample.shape[4]
+        if B > 1 and rows > MAX_BATCH_ROWS:
+            raise ValueError(f"batch of {B} clips of {tuple(sample.shape[1:])}: {rows} rows (B T h w) at the first level, above "
+                             f"the {MAX_BATCH_ROWS} = 32 x 72 x 128 rows this tape has been run at (MAX_BATCH_ROWS); "
+                             f"use a smaller batch and gradient accumulation")
+        return B, ts
+
+    def forward(self, sample: torch.Tensor, timestep, ehs: torch.Tensor, added_time_ids: torch.Tensor,
+                action_ids: torch.Tensor) -> torch.Tensor:
+        """sample (B,T,8,h,w); timestep a float (B = 1) or B of them; ehs (B,num_past_obs,Dctx); added_time_ids (B,3);
+        action_ids (B,T,Ch).  Returns (B,T,4,h,w) fp32.  The B samples are independent: rows are (b, t, s) everywhere,
+        M = B T h w, and every sample has its own timestep, noise_aug_strength, action ids and conditioning tokens (the
+        reference's loop shares `cond_sigmas[0]` at bsz > 1, train_svd.py:869).  B = 1 is the tape as it always was, launch for
+        launch.  B > 1 is refused above MAX_BATCH_ROWS first-level rows, and a mismatched B raises ValueError — both before
+        anything is launched."""
+        cfg, hip, dev, dt = self.cfg, self.hip, self.device, self.dt
+        B, timesteps = self._check_batch(sample, timestep, ehs, added_time_ids, action_ids)
+        self.B = B
         if getattr(self, "tape", None) is not None:
             self.tape.release()                         # a forward without a backward (evaluation) leaves its tape behind
         self.tape, self.grads = Tape(hip), {}
         T, ch, n, L = cfg.num_frames, cfg.block_out_channels, len(cfg.block_out_channels), cfg.layers_per_block
         _, _, cin, h, w = sample.shape
-        assert sample.shape[0] == 1 and sample.shape[1] == T
+        assert sample.shape[1] == T
         E = cfg.time_embed_dim
         # ---- conditioning embeddings (unet:447-487), a handful of rows
-        t_feat = torch.from_numpy(sinusoid(np.array([timestep], np.float32), ch[0])).to(dev, dt)
-        emb_t = self.mlp(_pad_rows(t_feat), "time_embedding", 1)
-        a = action_ids.float().reshape(T, -1)
+        t_feat = torch.from_numpy(sinusoid(np.array(timesteps, np.float32), ch[0])).to(dev, dt)
+        emb_t = self.mlp(_pad_rows(t_feat), "time_embedding", B)                  # per sample
+        a = action_ids.float().reshape(B * T, -1)
         feats = []
         for k in (1.0, 2.0, 4.0, 6.0, 8.0, 10.0):
             feats += [torch.cos(k * a), torch.sin(k * a)]
-        act = torch.stack(feats, dim=-1).reshape(T, -1)
+        act = torch.stack(feats, dim=-1).reshape(B * T, -1)
         Kp = self.W["add_action_proj.proj.weight"].shape[1]
-        act = torch.cat([act, act.new_zeros(T, Kp - act.shape[1])], dim=1).to(dev, dt)
-        emb_a = self.mlp(self.linear(_pad_rows(act), "add_action_proj.proj", T), "add_embedding_action", T)
+        act = torch.cat([act, act.new_zeros(B * T, Kp - act.shape[1])], dim=1).to(dev, dt)
+        emb_a = self.mlp(self.linear(_pad_rows(act), "add_action_proj.proj", B * T), "add_embedding_action", B * T)   # per (b, t)
         n_feat = torch.from_numpy(sinusoid(added_time_ids[:, -1].float().numpy(), cfg.addition_time_embed_dim)).to(dev, dt)
-        emb_n = self.mlp(_pad_rows(n_feat), "add_embedding_noise", 1)
-        emb = self.host_sum([emb_t, emb_a, emb_n], (T, E))
-        emb_silu = self.silu(self.cast16(emb))                                     # [64, E], rows >= T are silu(0) = 0
-        ehs16 = _pad_rows(ehs.reshape(self.num_past_obs, -1).to(dev, dt))
+        emb_n = self.mlp(_pad_rows(n_feat), "add_embedding_noise", B)             # per sample
+        emb = self.host_sum([emb_t, emb_a, emb_n], (B * T, E), groups=B)
+        emb_silu = self.silu(self.cast16(emb))                                     # [64 k, E], rows >= B T are silu(0) = 0
+        ehs16 = _pad_rows(ehs.reshape(B * self.num_past_obs, -1).to(dev, dt))
         # ---- conv_in
-        x0 = torch.zeros(T * h * w, CIN_PAD, dtype=dt, device=dev)
-        x0[:, :cin] = sample[0].permute(0, 2, 3, 1).reshape(-1, cin).to(dev, dt)
+        x0 = torch.zeros(B * T * h * w, CIN_PAD, dtype=dt, device=dev)
+        x0[:, :cin] = sample.reshape(B * T, cin, h, w).permute(0, 2, 3, 1).reshape(-1, cin).to(dev, dt)
         H, W = h, w
-        M = T * H * W
+        M = B * T * H * W
         x = self.conv(x0, "conv_in", M, H, W)
         skips = [(x, ch[0])]
         C = ch[0]
@@ -660,7 +706,7 @@ class UNetTrain:
                 skips.append((x, C))
             if i < n - 1:
                 H, W = H // 2, W // 2
-                M = T * H * W
+                M = B * T * H * W
                 x = self.conv(x, f"{p}.downsamplers.0.conv", M, H, W, mode=A_CONV3X3_S2)
                 skips.append((x, C))
         x = self._segment(self.res_block, "mid_block.resnets.0", x, C, C, M, H, W, T, emb_silu, 1e-5)
@@ -679,19 +725,19 @@ class UNetTrain:
             if i < n - 1:
                 x = self.upsample2x(x, M, H, W)
                 H, W = 2 * H, 2 * W
-                M = T * H * W
+                M = B * T * H * W
                 x = self.conv(x, f"{p}.upsamplers.0.conv", M, H, W)
         x = self.groupnorm(x, "conv_norm_out", M, H * W, 1e-5, True)
         y = self.conv(x, "conv_out", M, H, W)                                       # [M, 4] 16-bit
         self._out = y
-        return y.float().reshape(T, H, W, -1).permute(0, 3, 1, 2).unsqueeze(0)
+        return y.float().reshape(B, T, H, W, -1).permute(0, 1, 4, 2, 3)
 
     def backward(self, dpred: torch.Tensor, loss_scale: float = 1.0) -> Dict[str, torch.Tensor]:
-        """dpred: dL/d(model_pred) (1,T,4,h,w) fp32 -> {reference parameter name: fp32 gradient}.
+        """dpred: dL/d(model_pred) (B,T,4,h,w) fp32 -> {reference parameter name: fp32 gradient}.
         loss_scale: the 16-bit activation gradients are computed for loss_scale * L and the fp32 parameter gradients divided
         by it at the end — fp16's 6e-5 normal range loses the ~1e-5 activation gradients of a mean loss without it (the
         reference runs fp16 under accelerate's GradScaler, train_svd.py:699, 971-975); bf16 needs none."""
-        dy = (dpred[0].permute(0, 2, 3, 1).reshape(-1, dpred.shape[2]) * loss_scale).to(self.device, self.dt).contiguous()
+        dy = (dpred.reshape(-1, *dpred.shape[2:]).permute(0, 2, 3, 1).reshape(-1, dpred.shape[2]) * loss_scale).to(self.device, self.dt).contiguous()
         self.tape.run(self._out, dy)
         self._out = None
         if loss_scale != 1.0:
@@ -830,8 +876,9 @@ class EMAShadow:
 
 
 class Trainer:
-    """One fine-tuning step of the reference loop (`FTsvd/train_svd.py:844-970`) on one GPU, one sample per step:
-        prepare_step -> UNetTrain.forward -> wiw_edm_loss_grad -> UNetTrain.backward -> AdamW -> refreshed 16-bit operands.
+    """One fine-tuning step of the reference loop (`FTsvd/train_svd.py:844-970`) on one GPU, B >= 1 samples per step
+    (`--per_gpu_batch_size`; 1 is the reference's own setting):
+        prepare_step -> UNetTrain.forward -> wiw_edm_loss_grad[_batched] -> UNetTrain.backward -> AdamW -> refreshed 16-bit operands.
     Single process: `wiw_adamw_step` over every parameter tensor.  Data parallel: hand `optimizer=parallel.ShardedAdamW(...)`
     (gradients are copied into its flat buffer, reduced-scattered, the owned slices updated, parameters all-gathered)."""
 
@@ -905,6 +952,7 @@ class Trainer:
         self.scale_growth_interval, self._good_steps = int(scale_growth_interval), 0
         self.opt = optimizer
         self.steps = 0
+        self.last_sample_losses: list = []                     # per-sample losses of the last `step` (B floats)
         self.m = {k: torch.zeros_like(v) for k, v in net.master.items()} if optimizer is None else None
         self.v = {k: torch.zeros_like(v) for k, v in net.master.items()} if optimizer is None else None
         self._seen = None                                      # names that got a gradient in the previous step
@@ -1085,8 +1133,18 @@ class Trainer:
         acc = self._acc.get(name)
         return g if acc is None else acc + g
 
+    def _host_loss(self, loss: torch.Tensor) -> float:
+        """The step's one host read of the loss: per-sample values into `last_sample_losses`, their mean back."""
+        ls = [float(x) for x in loss.reshape(-1).tolist()]
+        self.last_sample_losses = ls
+        return ls[0] if len(ls) == 1 else sum(ls) / len(ls)
+
     def step(self, st) -> float:
-        """st: `train.StepInputs` of one micro-batch.  Returns its loss (host float)."""
+        """st: `train.StepInputs` of one micro-batch of B >= 1 samples (`train.collate`, `train.batch_from_pixels` of a loader
+        batch).  Returns its loss (host float): the mean of the B per-sample losses, which stay in `last_sample_losses` (B floats,
+        sum(...) / B is the returned value).  The gradient is that of the mean loss — the mean of the B single-sample gradients,
+        what `grad_accum = B` accumulates from single clips — so accumulation, loss scaling, clipping, the ZeRO-1 hand-over, the
+        EMA and the checkpoints see what they always saw."""
         from .train import TrainStep
 
         net, hip = self.net, self.net.hip
@@ -1128,7 +1186,7 @@ class Trainer:
                 self._micro, self._acc = 0, {}
                 if self.ema is not None:
                     self.ema.step(net.master)
-                return float(loss)
+                return self._host_loss(loss)
         elif self.scaling:
             bad = ~torch.stack([torch.isfinite(g).all() for g in grads.values()]).all()
             if self.opt is not None and self.opt.world > 1:                # EVERY rank skips, or none: the collectives of
@@ -1148,7 +1206,7 @@ class Trainer:
                     self.ema.step(net.master)                              # reference steps the EMA on a skipped update too (:979)
                 if self.max_grad_norm is not None:                         # a non-finite gradient has no finite norm
                     self._clip_rec, self._grad_norm, self._clip_coef = None, float("nan"), float("nan")
-                return float(loss)
+                return self._host_loss(loss)
         self._micro += 1
         if self._micro % self.grad_accum != 0:                             # not the last micro-batch: accumulate, no update
             inv = 1.0 / self.grad_accum
@@ -1157,7 +1215,7 @@ class Trainer:
                     g = g.reshape(net.master[name].shape) * inv
                     self._acc[name] = g if name not in self._acc else self._acc[name] + g
             net.grads = {}
-            return float(loss)
+            return self._host_loss(loss)
         if not overlapped and self.grad_accum > 1 and not clip_here:
             grads = {name: self._mean_grad(name, g) for name, g in grads.items() if self.trainable(name)}
         self._acc = {}
@@ -1185,7 +1243,7 @@ class Trainer:
             net.refresh(stale)                                             # the re-laid-out operands (convolutions, padded inputs)
             if self.ema is not None:
                 self.ema.step(net.master)
-            return float(loss)
+            return self._host_loss(loss)
         else:
             if not overlapped:                                           # first step, or fp16 (un-scaled after the backward)
                 for name, g in grads.items():
@@ -1201,7 +1259,7 @@ class Trainer:
         net.refresh()
         if self.ema is not None:
             self.ema.step(net.master)
-        return float(loss)
+        return self._host_loss(loss)
 
 
 def _pad_like(t: torch.Tensor, like: torch.Tensor) -> torch.Tensor:

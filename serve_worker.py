@@ -111,7 +111,8 @@ def build_worker(args, cfg: UNetConfig = None, vae_cfg: dict = None, clip=None) 
 
     worker = SVDWorker(denoise, fe, width=args.width, height=args.height, out_width=args.out_width,
                        out_height=args.out_height, num_frames=args.num_frames,
-                       num_inference_steps=args.num_inference_steps, task_type=cfg.task_type)
+                       num_inference_steps=args.num_inference_steps, task_type=cfg.task_type,
+                       device_resize=bool(getattr(args, "device_resize", False)))
     worker.bind_thread = unet.hip.bind_thread     # serve_tcp handler threads start on HIP device 0
     return worker
 

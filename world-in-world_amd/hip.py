@@ -229,16 +229,27 @@ EXPORTS_TRAIN_BATCH = {
                                             C.c_void_p, C.c_void_p, C.c_int]),
 }
 
+# include/wiw_resample.h: PIL-exact 8-bit image resampling (the two image resizes of a request), bound on the same two libraries
+_RESAMPLE_ARGS = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_int,
+                  C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+EXPORTS_RESAMPLE = {
+    "wiw_resample_u8_scratch_bytes": (C.c_int64, [C.c_int, C.c_int, C.c_int]),
+    "wiw_resample_u8": (C.c_int, list(_RESAMPLE_ARGS)),
+    "wiw_frames_resample_u8": (C.c_int, list(_RESAMPLE_ARGS)),
+    "wiw_u8_to_f32_lut": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+}
+
 
 def load_library(path: str = LIB_PATH) -> C.CDLL:
-    """dlopen the C-ABI library and declare every prototype of include/wiw_svd.h, include/wiw_cross_attn_train.h and
-    include/wiw_train_batch.h.  Raises if absent."""
+    """dlopen the C-ABI library and declare every prototype of include/wiw_svd.h, include/wiw_cross_attn_train.h,
+    include/wiw_train_batch.h and include/wiw_resample.h.  Raises if absent."""
     if not os.path.exists(path):
         raise RuntimeError(
             f"{path} not found: the HIP extension is required (build it with "
             f"`python world-in-world_amd/build.py`); there is no CPU or PyTorch fallback")
     lib = C.CDLL(path)
-    for name, (res, args) in (*EXPORTS.items(), *EXPORTS_CROSS_TRAIN.items(), *EXPORTS_TRAIN_BATCH.items()):
+    for name, (res, args) in (*EXPORTS.items(), *EXPORTS_CROSS_TRAIN.items(), *EXPORTS_TRAIN_BATCH.items(),
+                              *EXPORTS_RESAMPLE.items()):
         fn = getattr(lib, name)  # AttributeError if the symbol is missing
         fn.restype = res
         fn.argtypes = args
@@ -292,6 +303,8 @@ class Hip:
         self.sumsq_table_uploads = 0      # how often that table went to the device (tests / tools)
         # ... and this one for the non-GEMM kernels: (start_event, end_event, family, algorithmic_flops, algorithmic_bytes)
         self.kernel_profile = None
+        self._resample_tables = {}        # (in, out, filter) -> (coef, bounds, ksize) on the device, uploaded once per geometry
+        self._unit_lut = None             # fp32[256] on the device: byte -> 2 * (u / 255) - 1
 
     # ---- helpers
     def bind_thread(self) -> None:
@@ -838,6 +851,61 @@ class Hip:
         self._ck(self.lib.wiw_edm_loss_grad_batched(self._stream(), _p(pred), _p(noisy), _p(target), n, B, _p(sig), _p(grad),
                                                     _p(partial), nb), "wiw_edm_loss_grad_batched")
         return partial.sum(1) / n, grad
+
+    # ---- PIL-exact image resampling (csrc/resample.hip, include/wiw_resample.h)
+    def _resample_axis(self, in_size: int, out_size: int, filter: str):
+        """(coef, bounds, ksize) of one axis on the device, or (None, None, 0) for an unchanged side (the pass is skipped)."""
+        if in_size == out_size:
+            return None, None, 0
+        key = (int(in_size), int(out_size), filter)
+        if key not in self._resample_tables:
+            from .resample import pil_tables
+            coef, bounds = pil_tables(*key)
+            self._resample_tables[key] = (torch.from_numpy(coef.copy()).to(self.device), torch.from_numpy(bounds.copy()).to(self.device),
+                                          int(coef.shape[1]))
+        return self._resample_tables[key]
+
+    def _resample(self, entry, src, oh, ow, filter, out):
+        assert src.dim() == 3 and src.is_contiguous() and src.device == self.device
+        N, H, W = src.shape
+        if out is None:
+            out = torch.empty(N, oh, ow, dtype=torch.uint8, device=self.device)
+        assert out.dtype == torch.uint8 and tuple(out.shape) == (N, oh, ow) and out.is_contiguous()
+        ch, bh, kh = self._resample_axis(W, ow, filter)
+        cv, bv, kv = self._resample_axis(H, oh, filter)
+        scratch = None
+        if ch is not None and cv is not None:
+            scratch = torch.empty(self.lib.wiw_resample_u8_scratch_bytes(N, H, ow), dtype=torch.uint8, device=self.device)
+        self._ck(getattr(self.lib, entry)(self._stream(), _p(src), H * W, W, N, H, W, _p(out), oh * ow, ow, oh, ow, _p(ch), _p(bh), kh,
+                                          _p(cv), _p(bv), kv, _p(scratch)), entry)
+        return out
+
+    def resample_u8(self, src, oh, ow, filter, out=None):
+        """`Image.resize((ow, oh), filter)` of uint8 planes (N, H, W) -> uint8 (N, oh, ow), byte for byte; filter "bicubic" or
+        "lanczos".  The tables go to the device once per geometry.  Raises on a geometry the kernel refuses (> 64 taps)."""
+        assert src.dtype == torch.uint8
+        return self._resample("wiw_resample_u8", src, oh, ow, filter, out)
+
+    def frames_resample_u8(self, frames, oh, ow, filter, out=None):
+        """The same on fp32 planes (N, H, W) in [-1, 1] (decoded frames), quantised as `vae.frames_to_uint8_device` at the load."""
+        assert frames.dtype == torch.float32
+        return self._resample("wiw_frames_resample_u8", frames, oh, ow, filter, out)
+
+    def u8_to_f32_lut(self, src, lut=None, out=None):
+        """uint8 tensor -> fp32 tensor of the same shape through a 256-entry table; default: 2 * (u / 255) - 1, the table of
+        `resample.u8_to_unit_range_lut` (the host's own numpy expression, so the fp32 image is the host's bit for bit)."""
+        assert src.dtype == torch.uint8 and src.is_contiguous() and src.device == self.device
+        if lut is None:
+            if self._unit_lut is None:
+                from .resample import u8_to_unit_range_lut
+                self._unit_lut = torch.from_numpy(u8_to_unit_range_lut()).to(self.device)
+            lut = self._unit_lut
+        assert lut.dtype == torch.float32 and lut.numel() == 256 and lut.is_contiguous()
+        if out is None:
+            out = torch.empty(src.shape, dtype=torch.float32, device=self.device)
+        assert out.dtype == torch.float32 and out.shape == src.shape and out.is_contiguous()
+        self._ck(self.lib.wiw_u8_to_f32_lut(self._stream(), _p(src), src.numel(), _p(lut), _p(out)), "wiw_u8_to_f32_lut")
+        return out
 
     # ---- backward building blocks (row f2; csrc/train.hip)
     def colsum(self, X, rows, Cn, parts=None, units=1):

@@ -178,6 +178,23 @@ def build_response(video: np.ndarray, b_action, save_dirs: List[str], return_obj
     return {"save_dirs": save_dirs}
 
 
+def build_response_u8(video_u8: np.ndarray, b_action, save_dirs: List[str], return_objects: bool) -> dict:
+    """`build_response` for frames that already ARE the resized uint8 bytes (B, T, 3, H, W) (the device resize): the
+    truncation (clip(float32(u) / 255, 0, 1) * 255).astype(uint8) is the identity on all 256 values, so `pred_frames` is the
+    array itself; the JPEG writer gets the same u / 255 floats as on the host path (it rounds u / 255 * 255 + 0.5 back to u)."""
+    video_u8 = np.asarray(video_u8)
+    assert video_u8.dtype == np.uint8 and video_u8.ndim == 5
+    if return_objects:
+        return {"pred_frames": video_u8, "save_dirs": save_dirs}
+    save_predict(video_u8.astype(np.float32) / 255.0, b_action, save_dirs)
+    return {"save_dirs": save_dirs}
+
+
+def image_to_u8_planes(img: Image.Image) -> np.ndarray:
+    """PIL image -> uint8 (3, H0, W0): the bytes `preprocess_image` / `image_to_array` start from."""
+    return np.ascontiguousarray(np.transpose(np.asarray(img.convert("RGB"), dtype=np.uint8), (2, 0, 1)))
+
+
 def split_batch(tasks: dict, bs: int):
     """Batcher.split_batch (worker_manager.py:448-469): every value is sliced v[start:start+bs]."""
     n = len(next(iter(tasks.values())))

@@ -21,6 +21,7 @@ Two transports:
 from __future__ import annotations
 
 import argparse
+import logging
 import os
 import socket
 import sys
@@ -29,9 +30,12 @@ from typing import Callable, Optional, Protocol
 
 import numpy as np
 
+from ..resample import MAX_TAPS, supported
 from . import plumbing as P
 from .protocol import DONE, read_framed, read_pickled, write_framed, write_pickled
 
+
+log = logging.getLogger(__name__)
 
 MAX_NUM_FRAMES = 32   # frame slots of the temporal attention kernels (csrc/temporal32.hip); `validate_args` refuses more
 VAE_WIDEST_ROW_BYTES = 128 * 2   # the temporal decoder's last level: 128 channels, 16-bit, at the full output resolution
@@ -49,13 +53,29 @@ class Frontend(Protocol):
     def decode(self, latents: np.ndarray) -> np.ndarray:
         """latents (B,T,4,h,w) -> frames (B,T,3,H,W) in [-1,1] float32 (decode_latents, pipeline:282-309)."""
 
+    # Optional (the device resize, `SVDWorker(device_resize=True)`; `vae.HIPFrontend` has both):
+    #   encode_uint8(images_u8, image_noise, noise_aug_strength, size): images_u8 = list of B uint8 (3,H0,W0) arrays, size =
+    #       (width, height); the LANCZOS resize and the [-1,1] conversion of both branches happen behind it; same returns
+    #       as `encode(preprocess_image(...), ..., clip_images=...)`, bit for bit;
+    #   decode_resized_uint8(latents, out_size, filter="bicubic") -> uint8 (B,T,3,oh,ow): decode, frame quantisation and
+    #       the PIL resize to out_size = (ow, oh); the bytes of `decode` + `frames_to_pil` + `images_to_tensor`.
+
 
 class SVDWorker:
     def __init__(self, denoise_fn: Callable[..., "np.ndarray"], frontend: Frontend, *, width=1024, height=576,
                  out_width=480, out_height=480, num_frames=14, num_inference_steps=30, seed=1,
-                 world_model_name=P.WORLD_MODEL_NAME, noise_fn: Optional[Callable] = None, task_type: str = "navigation"):
+                 world_model_name=P.WORLD_MODEL_NAME, noise_fn: Optional[Callable] = None, task_type: str = "navigation",
+                 device_resize: bool = False):
+        """device_resize: both image resizes of a request (LANCZOS in, BICUBIC out) run behind the frontend's
+        `encode_uint8` / `decode_resized_uint8` (PIL's integer arithmetic on the device: the same bytes) instead of in PIL on
+        the host; taken with a frontend that has both methods (otherwise one logged line and the host path).  A geometry those
+        kernels refuse (more than 64 taps: a side shrunk by more than ~10x) is served by the host path for that request.
+        False: nothing differs from the host path."""
         self.denoise_fn = denoise_fn
         self.frontend = frontend
+        self.device_resize = bool(device_resize) and hasattr(frontend, "encode_uint8") and hasattr(frontend, "decode_resized_uint8")
+        if device_resize and not self.device_resize:
+            log.warning("device_resize: the frontend has no encode_uint8 / decode_resized_uint8; requests take the host (PIL) path")
         self.width, self.height = width, height
         self.out_size = (out_width, out_height)
         self.num_frames = num_frames
@@ -74,6 +94,11 @@ class SVDWorker:
         b_action, save_dirs, return_objects, images = P.parse_request(request, self.world_model_name)
         b_action = P.check_b_action(b_action, self.num_frames, self.task_type)
         B = len(images)
+        if self.device_resize:
+            if self._device_resize_serves(images):
+                return self._call_device_resize(images, b_action, save_dirs, return_objects)
+            log.warning("device_resize: a resize of this request needs more than %d taps per sample; served by the host (PIL) path",
+                        MAX_TAPS)
         x = np.stack([P.preprocess_image(im, self.width, self.height) for im in images])
         # CLIP sees the image at its ORIGINAL size (pipeline:192-199); only the VAE branch is resized (pipeline:521)
         clip_images = None
@@ -98,6 +123,30 @@ class SVDWorker:
             clips = [P.frames_to_pil(f) for f in frames]
         video = P.images_to_tensor(clips, save_size=self.out_size)
         out = P.build_response(video, b_action, list(save_dirs), return_objects)
+        P.check_outputdict(out)
+        return out
+
+    def _device_resize_serves(self, images) -> bool:
+        """Whether the resampling kernels take every resize of this request (`resample.supported`: at most 64 taps a sample)."""
+        ow, oh = self.out_size
+        sides = [(self.width, ow, "bicubic"), (self.height, oh, "bicubic")]
+        for im in images:
+            sides += [(im.size[0], self.width, "lanczos"), (im.size[1], self.height, "lanczos")]
+        return all(supported(*s) for s in set(sides))
+
+    def _call_device_resize(self, images, b_action, save_dirs, return_objects) -> dict:
+        """`__call__` with both resizes behind the frontend: same draws (order and shapes), same denoise call, same bytes."""
+        B = len(images)
+        images_u8 = [P.image_to_u8_planes(im) for im in images]
+        img_noise = self.noise_fn((B, 3, self.height, self.width))           # draw 1 (pipeline:522)
+        image_latents, image_embeddings = self.frontend.encode_uint8(images_u8, img_noise, 0.02, (self.width, self.height))
+        h, w = image_latents.shape[-2:]
+        lat_noise = self.noise_fn((B, self.num_frames, 4, h, w))             # draw 2 (pipeline:765)
+        latents = self.denoise_fn(image_latents, image_embeddings, lat_noise, b_action,
+                                  num_steps=self.num_inference_steps, fps=7, motion_bucket_id=127,
+                                  noise_aug_strength=0.02)
+        video_u8 = self.frontend.decode_resized_uint8(latents, self.out_size, "bicubic")
+        out = P.build_response_u8(video_u8, b_action, list(save_dirs), return_objects)
         P.check_outputdict(out)
         return out
 
@@ -343,6 +392,10 @@ def build_arg_parser() -> argparse.ArgumentParser:
     ap.add_argument("--residual_fp32_full", action="store_true",
                     help="with --residual_fp32: also the hidden stream inside the transformer blocks in fp32 (rounds 4-5's form of "
                          "the mode: 5.1e-4 / 8.6e-4 on the same trajectory at 0.90x the speed of fp16)")
+    ap.add_argument("--device_resize", action=argparse.BooleanOptionalAction, default=False,
+                    help="resize the conditioning image (LANCZOS) and the decoded frames (BICUBIC) on the GPU with PIL's integer "
+                         "arithmetic (csrc/resample.hip: the same bytes) instead of in PIL on the host; the frames leave the GPU once, "
+                         "already (T, 3, out_height, out_width) uint8.  OFF by default")
     ap.add_argument("--batch_size", type=int, default=0)
     ap.add_argument("--coalesce_candidates", type=int, default=0,
                     help="> 0: batch requests of different clients into one GPU call of up to this many candidates")

@@ -333,8 +333,8 @@ class HIPFrontend:
 
     def _embed(self, x: torch.Tensor, clip_images) -> torch.Tensor:
         """(B,1,D) fp32 CLIP image embeddings; `clip_images` = per-candidate un-resized images (pipeline:192-199) or None."""
-        groups = [x] if clip_images is None else [torch.from_numpy(np.ascontiguousarray(c))[None].to(self.device, torch.float32)
-                                                   for c in clip_images]
+        groups = [x] if clip_images is None else [(c if torch.is_tensor(c) else torch.from_numpy(np.ascontiguousarray(c)))[None]
+                                                   .to(self.device, torch.float32) for c in clip_images]
         if clip_images is not None and len({tuple(g.shape) for g in groups}) == 1:
             groups = [torch.cat(groups)]                     # same size (the normal case): one batched pass
         if self.clip_hip is not None:
@@ -354,9 +354,56 @@ class HIPFrontend:
         return lat.cpu().numpy(), emb.cpu().numpy()
 
     @torch.no_grad()
+    def encode_uint8(self, images_u8, image_noise: np.ndarray, noise_aug_strength: float, size):
+        """`encode` from the request's bytes: images_u8 = list of B uint8 arrays (3, H0, W0), size = (width, height) of the
+        model.  The bytes are uploaded (1 byte per sample instead of 4); on the device each image is LANCZOS-resized to `size`
+        with PIL's integer arithmetic (`Hip.resample_u8`; skipped when the size already matches) and mapped to fp32 [-1, 1]
+        through the 256-entry table of the host's own `2 * (u / 255) - 1` (the VAE branch, pipeline:521); the CLIP branch gets
+        the UN-resized image through the same table (pipeline:192-199).  Latents and embeddings are bit-equal to
+        `encode(preprocess_image(...), ..., clip_images=[image_to_array(...)])`.  Raises (before any launch) on a geometry the
+        resampling kernel refuses (`resample.supported`)."""
+        from .resample import supported
+        hip = self.vae.hip
+        width, height = size
+        for im in images_u8:
+            if not (supported(im.shape[2], width, "lanczos") and supported(im.shape[1], height, "lanczos")):
+                raise ValueError(f"encode_uint8: {im.shape[2]}x{im.shape[1]} -> {width}x{height} needs more than 64 taps")
+        raw, vae_in = [], []
+        for im in images_u8:
+            u = torch.from_numpy(np.ascontiguousarray(im[:3])).to(self.device)
+            raw.append(u)
+            vae_in.append(u if tuple(u.shape[1:]) == (height, width) else hip.resample_u8(u, height, width, "lanczos"))
+        x = hip.u8_to_f32_lut(torch.stack(vae_in))
+        clip_images = None
+        if any(tuple(u.shape[1:]) != (height, width) for u in raw):
+            clip_images = [hip.u8_to_f32_lut(u) for u in raw]
+        emb = self._embed(x, clip_images)
+        xn = x + noise_aug_strength * torch.from_numpy(np.ascontiguousarray(image_noise)).to(self.device, torch.float32)
+        lat = self.vae.encode_mode(xn)
+        if self.device_io:
+            return lat, emb
+        return lat.cpu().numpy(), emb.cpu().numpy()
+
+    @torch.no_grad()
     def decode(self, latents) -> np.ndarray:
         z = latents if torch.is_tensor(latents) else torch.from_numpy(np.ascontiguousarray(latents))
         return self.vae.decode(z).cpu().numpy()
+
+    @torch.no_grad()
+    def decode_resized_uint8(self, latents, out_size, filter: str = "bicubic") -> np.ndarray:
+        """decode + frame quantisation + PIL resize to out_size = (ow, oh), all on the device: uint8 (B, T, 3, oh, ow) on the
+        host, the response's own layout.  `Hip.frames_resample_u8` quantises the fp32 frames at its loads (the arithmetic of
+        `frames_to_uint8_device`) and resamples with PIL's integer tables, so the bytes are those of `decode_uint8` + `Image.resize`;
+        no (T, H, W, 3) uint8 copy is made and oh * ow * 3 * T bytes per candidate cross PCIe."""
+        z = latents if torch.is_tensor(latents) else torch.from_numpy(np.ascontiguousarray(latents))
+        ow, oh = out_size
+        out = []
+        for b in range(z.shape[0]):          # per clip: bounds the fp32 frame buffer to one candidate
+            frames = self.vae.decode(z[b:b + 1])[0]
+            T, Cc, H, W = frames.shape
+            u8 = self.vae.hip.frames_resample_u8(frames.reshape(T * Cc, H, W), oh, ow, filter)
+            out.append(u8.reshape(T, Cc, oh, ow).cpu().numpy())
+        return np.stack(out)
 
     @torch.no_grad()
     def decode_uint8(self, latents: np.ndarray) -> np.ndarray:

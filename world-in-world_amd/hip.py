@@ -239,17 +239,25 @@ EXPORTS_RESAMPLE = {
     "wiw_u8_to_f32_lut": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
 }
 
+# include/wiw_metrics.h: per-plane SSIM and squared error (the frame metrics of a validation pass), bound on the same two libraries
+METRICS_F32, METRICS_U8 = 0, 1
+EXPORTS_METRICS = {
+    "wiw_frame_metrics_partials": (C.c_int64, [C.c_int, C.c_int, C.c_int]),
+    "wiw_frame_metrics": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_int, C.c_int64, C.c_int64,
+                                    C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+}
+
 
 def load_library(path: str = LIB_PATH) -> C.CDLL:
     """dlopen the C-ABI library and declare every prototype of include/wiw_svd.h, include/wiw_cross_attn_train.h,
-    include/wiw_train_batch.h and include/wiw_resample.h.  Raises if absent."""
+    include/wiw_train_batch.h, include/wiw_resample.h and include/wiw_metrics.h.  Raises if absent."""
     if not os.path.exists(path):
         raise RuntimeError(
             f"{path} not found: the HIP extension is required (build it with "
             f"`python world-in-world_amd/build.py`); there is no CPU or PyTorch fallback")
     lib = C.CDLL(path)
     for name, (res, args) in (*EXPORTS.items(), *EXPORTS_CROSS_TRAIN.items(), *EXPORTS_TRAIN_BATCH.items(),
-                              *EXPORTS_RESAMPLE.items()):
+                              *EXPORTS_RESAMPLE.items(), *EXPORTS_METRICS.items()):
         fn = getattr(lib, name)  # AttributeError if the symbol is missing
         fn.restype = res
         fn.argtypes = args
@@ -305,6 +313,7 @@ class Hip:
         self.kernel_profile = None
         self._resample_tables = {}        # (in, out, filter) -> (coef, bounds, ksize) on the device, uploaded once per geometry
         self._unit_lut = None             # fp32[256] on the device: byte -> 2 * (u / 255) - 1
+        self._metrics_lut = None          # fp32[256] on the device: byte -> float32(u) / float32(255), uploaded once
 
     # ---- helpers
     def bind_thread(self) -> None:
@@ -905,6 +914,31 @@ class Hip:
             out = torch.empty(src.shape, dtype=torch.float32, device=self.device)
         assert out.dtype == torch.float32 and out.shape == src.shape and out.is_contiguous()
         self._ck(self.lib.wiw_u8_to_f32_lut(self._stream(), _p(src), src.numel(), _p(lut), _p(out)), "wiw_u8_to_f32_lut")
+        return out
+
+    # ---- frame metrics (csrc/metrics.hip, include/wiw_metrics.h)
+    def frame_metrics(self, a, b, out=None):
+        """Per-plane (mean SSIM, sum of squared differences) of device tensors a, b (N, H, W), each fp32 in [0, 1] or uint8 (a
+        byte u counts as float32(u) / float32(255), the reference's `to_tensor` value, through a table uploaded once), contiguous
+        or strided with unit stride along W -> float64 (N, 2) on the device.  All arithmetic is fp64; no atomics: bit-repeatable,
+        and a plane's row does not depend on the other planes.  Raises on planes smaller than the 11 x 11 window."""
+        assert a.dim() == 3 and a.shape == b.shape and a.device == self.device and b.device == self.device
+        N, H, W = a.shape
+        ops = []
+        for t in (a, b):
+            assert t.dtype in (torch.float32, torch.uint8), t.dtype
+            assert t.stride(2) == 1 or W == 1, "frame_metrics: unit stride along W"
+            plane = t.stride(0) if N > 1 else H * t.stride(1)          # the stride of a one-element dimension means nothing
+            ops += [_p(t), METRICS_U8 if t.dtype == torch.uint8 else METRICS_F32, plane, t.stride(1)]
+        if self._metrics_lut is None:
+            import numpy as np
+            self._metrics_lut = torch.from_numpy(np.arange(256, dtype=np.float32) / np.float32(255)).to(self.device)
+        partials = torch.empty(max(self.lib.wiw_frame_metrics_partials(N, H, W), 1), dtype=torch.float64, device=self.device)
+        if out is None:
+            out = torch.empty(N, 2, dtype=torch.float64, device=self.device)
+        assert out.dtype == torch.float64 and tuple(out.shape) == (N, 2) and out.is_contiguous()
+        self._ck(self.lib.wiw_frame_metrics(self._stream(), *ops, _p(self._metrics_lut), N, H, W, _p(partials), _p(out)),
+                 "wiw_frame_metrics")
         return out
 
     # ---- backward building blocks (row f2; csrc/train.hip)

@@ -1058,7 +1058,7 @@ class Trainer:
 
     @torch.no_grad()
     def validate(self, samples, num_steps: int = 25, use_ema: Optional[bool] = None, frontend=None, log_path: Optional[str] = None,
-                 residual_fp32: bool = False) -> dict:
+                 residual_fp32: bool = False, frame_metrics: bool = False) -> dict:
         """The validation pass of the training loop (train_svd.py:996-1030 -> eval_inference :1140-1193): the INFERENCE loop on
         the current weights — the EMA weights under `--use_ema` (:1004-1007; the live ones come back afterwards, :1189-1191) —
         over `samples`, with the reference's knobs (fps 7, motion bucket 127, noise_aug 0.02), and its per-clip PSNR
@@ -1067,7 +1067,14 @@ class Trainer:
         samples: dicts with image_latents (1,4,h,w), image_embeddings (1,1,D), noise (1,T,4,h,w), actions (1,T) and the
         ground truth `target_latents` (1,T,4,h,w) [+ `target_frames` (1,T,3,H,W) in [0,1] when a `frontend` decodes].
         Returns {"global_step", "latent_mse", "latent_psnr", ["psnr"], "clips"}; appended as one JSON line to `log_path`
-        (`accelerator.log(log_dict, step=global_step)`)."""
+        (`accelerator.log(log_dict, step=global_step)`).
+        frame_metrics=True (with a `frontend` and `target_frames`): the record also gets what the reference logs from
+        `evaluate_video_metrics(gt, gen, only_final=True)` (train_svd.py:1176-1187) for the metrics that need no network —
+        "ssim" / "ssim_std" and "frame_psnr" / "frame_psnr_std": mean and population standard deviation over all clips and
+        frames of the per-frame SSIM and PSNR (`metrics.frame_scores`).  The decoded clip is quantised to uint8 as the
+        reference's generated frames are (`vae.frames_to_uint8_device`), stays on the device and is compared with the ground
+        truth there (csrc/metrics.hip).  "psnr" keeps its definition (un-quantised frames, on the host) either way, and with
+        frame_metrics=False the record and the launches are what they were."""
         import json
         import math
 
@@ -1081,6 +1088,7 @@ class Trainer:
                        num_past_obs=getattr(self.net, "num_past_obs", 1))
         den = SVDDenoiser(unet, use_graph=False)
         se, n, psnrs, lat_psnrs = 0.0, 0, [], []
+        frame_ssim, frame_psnr = [], []
         for s in samples:
             lat = den.denoise(s["image_latents"], s["image_embeddings"], s["noise"], s["actions"], num_steps=num_steps, fps=7,
                               motion_bucket_id=127, noise_aug_strength=0.02)
@@ -1091,7 +1099,19 @@ class Trainer:
             mse = float(d.pow(2).mean())
             lat_psnrs.append(100.0 if mse < 1e-10 else 20 * math.log10(rng / math.sqrt(mse)))
             if frontend is not None and "target_frames" in s:
-                fr = torch.as_tensor(frontend.decode(lat.cpu().numpy() if not hasattr(frontend, "decode_frames") else lat))
+                if frame_metrics and hasattr(frontend, "decode_device"):      # the frames stay in HBM for the device metrics
+                    fr = frontend.decode_device(lat)
+                else:
+                    fr = torch.as_tensor(frontend.decode(lat.cpu().numpy() if not hasattr(frontend, "decode_frames") else lat))
+                if frame_metrics:
+                    from .metrics import frame_scores
+                    from .vae import frames_to_uint8_device
+
+                    dev = self.net.hip.device
+                    gen = torch.stack([frames_to_uint8_device(c.to(dev, torch.float32)).permute(0, 3, 1, 2) for c in fr])
+                    gt_dev = torch.as_tensor(s["target_frames"]).to(dev, torch.float32).reshape(gen.shape)
+                    f_ssim, f_psnr = frame_scores(self.net.hip, gt_dev, gen)
+                    frame_ssim.extend(f_ssim.reshape(-1).tolist()); frame_psnr.extend(f_psnr.reshape(-1).tolist())
                 fr = (fr.float().cpu() / 2 + 0.5).clamp(0, 1)                    # postprocess_video (video_processor.py:90-113)
                 gt = torch.as_tensor(s["target_frames"]).float().cpu()
                 for a, b in zip(fr.reshape(-1, *fr.shape[-3:]), gt.reshape(-1, *gt.shape[-3:])):
@@ -1101,6 +1121,9 @@ class Trainer:
                "latent_mse": se / max(n, 1), "latent_psnr": float(sum(lat_psnrs) / max(len(lat_psnrs), 1))}
         if psnrs:
             out["psnr"] = float(sum(psnrs) / len(psnrs))
+        if frame_ssim:                                                        # evaluate_video_metrics(..., only_final=True)
+            out.update({"ssim": float(np.mean(frame_ssim)), "ssim_std": float(np.std(frame_ssim)),
+                        "frame_psnr": float(np.mean(frame_psnr)), "frame_psnr_std": float(np.std(frame_psnr))})
         if log_path:
             with open(log_path, "a") as f:
                 f.write(json.dumps(out) + "\n")

@@ -390,6 +390,13 @@ class HIPFrontend:
         return self.vae.decode(z).cpu().numpy()
 
     @torch.no_grad()
+    def decode_device(self, latents) -> torch.Tensor:
+        """`decode` without the copy to the host: fp32 frames (B, T, 3, H, W) in [-1, 1] on the device (the validation pass
+        computes its frame metrics there)."""
+        z = latents if torch.is_tensor(latents) else torch.from_numpy(np.ascontiguousarray(latents))
+        return self.vae.decode(z)
+
+    @torch.no_grad()
     def decode_resized_uint8(self, latents, out_size, filter: str = "bicubic") -> np.ndarray:
         """decode + frame quantisation + PIL resize to out_size = (ow, oh), all on the device: uint8 (B, T, 3, oh, ow) on the
         host, the response's own layout.  `Hip.frames_resample_u8` quantises the fp32 frames at its loads (the arithmetic of

@@ -95,26 +95,41 @@ def build_worker(args, cfg: UNetConfig = None, vae_cfg: dict = None, clip=None) 
     # the default here since round 6) or bf16 (BASELINE's dtype) — libwiwsvd_f16.so / libwiwsvd.so.  fp32 is not a serving dtype of
     # this path (the reference upcasts only the VAE encoder, pipeline:525-527).
     dname, res32 = resolve_precision(args)     # float16 + the block-level fp32 residual stream unless told otherwise
-    dtype = getattr(torch, dname)
-    unet = UNetHIP(cfg, unet_sd, args.device, dtype=dtype, residual_fp32=res32)
-    den = SVDDenoiser(unet, use_graph=bool(args.hip_graph))   # graph replay by default, as bench.py measures
-    clip = clip if clip is not None else _clip(args.svd_path, args.random_weights)
-    # VAE and CLIP on the HIP kernels (vae.py, clip.py: HIPFrontend builds `CLIPVisionHIP` from the `transformers` module's
-    # weights).  There is no PyTorch / MIOpen route in the product (the VAE alone needed > 6 minutes per decode on a fresh
-    # box); the fp32 PyTorch chain lives in oracle/.
-    fe = HIPFrontend(VAEHIP(vae_sd, args.device, hip=unet.hip, **vae_cfg), clip, dtype=dtype, device_io=True)
+    guard = getattr(args, "finite_guard", "off")
+    clips = [clip]          # the `transformers` module both chains read their CLIP weights from, loaded once
 
-    def denoise(image_latents, image_embeddings, noise, actions, **kw):
-        # device tensors in (HIPFrontend.encode, device_io) and out (decode_uint8 takes them): no host bounce of latents
-        return den.denoise(torch.as_tensor(image_latents), torch.as_tensor(image_embeddings), torch.as_tensor(noise),
-                           actions, **kw)
+    def chain(dtype, res32, use_graph, **guard_kw) -> SVDWorker:
+        unet = UNetHIP(cfg, unet_sd, args.device, dtype=dtype, residual_fp32=res32)
+        den = SVDDenoiser(unet, use_graph=use_graph)
+        if clips[0] is None:
+            clips[0] = _clip(args.svd_path, args.random_weights)
+        clip = clips[0]
+        # VAE and CLIP on the HIP kernels (vae.py, clip.py: HIPFrontend builds `CLIPVisionHIP` from the `transformers` module's
+        # weights).  There is no PyTorch / MIOpen route in the product (the VAE alone needed > 6 minutes per decode on a fresh
+        # box); the fp32 PyTorch chain lives in oracle/.
+        fe = HIPFrontend(VAEHIP(vae_sd, args.device, hip=unet.hip, **vae_cfg), clip, dtype=dtype, device_io=True)
 
-    worker = SVDWorker(denoise, fe, width=args.width, height=args.height, out_width=args.out_width,
-                       out_height=args.out_height, num_frames=args.num_frames,
-                       num_inference_steps=args.num_inference_steps, task_type=cfg.task_type,
-                       device_resize=bool(getattr(args, "device_resize", False)))
-    worker.bind_thread = unet.hip.bind_thread     # serve_tcp handler threads start on HIP device 0
-    return worker
+        def denoise(image_latents, image_embeddings, noise, actions, **kw):
+            # device tensors in (HIPFrontend.encode, device_io) and out (decode_uint8 takes them): no host bounce of latents
+            return den.denoise(torch.as_tensor(image_latents), torch.as_tensor(image_embeddings), torch.as_tensor(noise),
+                               actions, **kw)
+
+        worker = SVDWorker(denoise, fe, width=args.width, height=args.height, out_width=args.out_width,
+                           out_height=args.out_height, num_frames=args.num_frames,
+                           num_inference_steps=args.num_inference_steps, task_type=cfg.task_type,
+                           device_resize=bool(getattr(args, "device_resize", False)), **guard_kw)
+        worker.bind_thread = unet.hip.bind_thread     # serve_tcp handler threads start on HIP device 0
+        return worker
+
+    guard_kw = {}
+    if guard != "off":
+        guard_kw["finite_guard"] = guard
+    if guard == "fallback":
+        # the second chain of --finite_guard fallback: the same weights in bfloat16 (fp32's exponent range), as a bfloat16
+        # worker runs them (no fp32 residual stream), launched eagerly — it serves the rare bad candidate, a captured graph
+        # per candidate count would pin HBM for it.  It is handed the first chain's draws, never its own.
+        guard_kw["fallback"] = chain(torch.bfloat16, False, False)
+    return chain(getattr(torch, dname), res32, bool(args.hip_graph), **guard_kw)   # graph replay by default, as bench.py measures
 
 
 def main(argv=None) -> None:

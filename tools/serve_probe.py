@@ -1,5 +1,5 @@
 """Phase timing of one full-size request through the launcher's worker (random-init weights).
-usage: python tools/serve_probe.py [n_requests] [candidates] [--device_resize]
+usage: python tools/serve_probe.py [n_requests] [candidates] [--device_resize] [--finite_guard=off|error|fallback]
 
 Rows per request: frontend.encode (CLIP + VAE encoder; with --device_resize also the upload of the bytes and the LANCZOS
 resize), denoise, vae.decode (summed over the candidates), and post-decode = everything between the end of the loop and the
@@ -17,13 +17,14 @@ import serve_worker  # noqa: E402
 
 
 def main():
-    argv = [a for a in sys.argv[1:] if a != "--device_resize"]
+    guard = [a for a in sys.argv[1:] if a.startswith("--finite_guard=")]          # the worker's finite guard (off by default)
+    argv = [a for a in sys.argv[1:] if a != "--device_resize" and a not in guard]
     device_resize = "--device_resize" in sys.argv[1:]
     nreq = int(argv[0]) if len(argv) > 0 else 2
     B = int(argv[1]) if len(argv) > 1 else 1
     t0 = time.time()
     args = serve_worker.arg_parser().parse_args(["--random_weights", "--num_inference_steps", "2", "--port", "1"] +
-                                                (["--device_resize"] if device_resize else []))
+                                                (["--device_resize"] if device_resize else []) + guard)
     w = serve_worker.build_worker(args)
     torch.cuda.synchronize()
     print(f"[probe] build_worker {time.time() - t0:.1f}s  device_resize={getattr(w, 'device_resize', False)}", flush=True)

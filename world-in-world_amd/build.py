@@ -16,7 +16,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libwiwsvd.so")
 LIB_F16 = os.path.join(HERE, "libwiwsvd_f16.so")
 VARIANTS = [(LIB, "build", []), (LIB_F16, "build_f16", ["-DWIW_F16=1"])]
-SOURCES = ["gemm.hip", "gemm_huge.hip", "ffn.hip", "ffn32.hip", "attention.hip", "attention32.hip", "cross_attn.hip", "cross_attn_bwd.hip", "temporal.hip", "temporal32.hip", "clip.hip", "norm.hip", "elementwise.hip", "vae.hip", "train.hip", "train_batch.hip", "resample.hip", "metrics.hip"]
+SOURCES = ["gemm.hip", "gemm_huge.hip", "ffn.hip", "ffn32.hip", "attention.hip", "attention32.hip", "cross_attn.hip", "cross_attn_bwd.hip", "temporal.hip", "temporal32.hip", "clip.hip", "norm.hip", "elementwise.hip", "vae.hip", "train.hip", "train_batch.hip", "resample.hip", "metrics.hip", "range.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 # per-file extras: the attention softmax never sees NaNs (infinities are used and preserved); dropping NaN
@@ -29,7 +29,7 @@ def _stale(lib: str) -> bool:
     if not os.path.exists(lib):
         return True
     t = os.path.getmtime(lib)
-    deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC)] + [os.path.join(HERE, "..", "include", h) for h in ("wiw_svd.h", "wiw_cross_attn_train.h", "wiw_train_batch.h", "wiw_resample.h", "wiw_metrics.h")]
+    deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC)] + [os.path.join(HERE, "..", "include", h) for h in ("wiw_svd.h", "wiw_cross_attn_train.h", "wiw_train_batch.h", "wiw_resample.h", "wiw_metrics.h", "wiw_range.h")]
     return any(os.path.getmtime(d) > t for d in deps)
 
 

@@ -27,6 +27,7 @@ import torch
 
 from .frontend import CLIP_MEAN, CLIP_STD
 from .hip import EPI_GELU, EPI_OUT_F32, EPI_QUICK_GELU, Hip, TiledW
+from .range import scoped
 
 
 def gaussian_taps(in_size: int, out_size: int):
@@ -124,6 +125,7 @@ class CLIPVisionHIP:
 
     # ------------------------------------------------------------------------------------------
     @torch.no_grad()
+    @scoped("clip")
     def embed_pixels(self, images: torch.Tensor) -> torch.Tensor:
         """images (B,3,H0,W0) fp32 in [-1,1] at their OWN size -> image_embeds (B, projection_dim) fp32."""
         hip, w, C, Sp = self.hip, self.w, self.C, self.Sp

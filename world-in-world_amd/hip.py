@@ -247,17 +247,32 @@ EXPORTS_METRICS = {
                                     C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
 }
 
+# include/wiw_range.h: per-segment value-range statistics (the serving guard and the range probe), bound on the same two libraries
+RANGE_BINS = 64
+
+
+class WiwRangeStats(C.Structure):
+    _fields_ = [("n_nan", C.c_uint64), ("n_inf", C.c_uint64), ("n_zero", C.c_uint64), ("n_hot", C.c_uint64), ("n_tiny", C.c_uint64),
+                ("absmax", C.c_float), ("absmin", C.c_float)]
+
+
+EXPORTS_RANGE = {
+    "wiw_range_stats_partials": (C.c_int64, [C.c_int64, C.c_int, C.c_int64, C.c_int]),
+    "wiw_range_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_int64, C.c_int64, C.c_float, C.c_float,
+                                  C.c_void_p, C.c_void_p, C.c_void_p]),
+}
+
 
 def load_library(path: str = LIB_PATH) -> C.CDLL:
     """dlopen the C-ABI library and declare every prototype of include/wiw_svd.h, include/wiw_cross_attn_train.h,
-    include/wiw_train_batch.h, include/wiw_resample.h and include/wiw_metrics.h.  Raises if absent."""
+    include/wiw_train_batch.h, include/wiw_resample.h, include/wiw_metrics.h and include/wiw_range.h.  Raises if absent."""
     if not os.path.exists(path):
         raise RuntimeError(
             f"{path} not found: the HIP extension is required (build it with "
             f"`python world-in-world_amd/build.py`); there is no CPU or PyTorch fallback")
     lib = C.CDLL(path)
     for name, (res, args) in (*EXPORTS.items(), *EXPORTS_CROSS_TRAIN.items(), *EXPORTS_TRAIN_BATCH.items(),
-                              *EXPORTS_RESAMPLE.items(), *EXPORTS_METRICS.items()):
+                              *EXPORTS_RESAMPLE.items(), *EXPORTS_METRICS.items(), *EXPORTS_RANGE.items()):
         fn = getattr(lib, name)  # AttributeError if the symbol is missing
         fn.restype = res
         fn.argtypes = args
@@ -314,6 +329,9 @@ class Hip:
         self._resample_tables = {}        # (in, out, filter) -> (coef, bounds, ksize) on the device, uploaded once per geometry
         self._unit_lut = None             # fp32[256] on the device: byte -> 2 * (u / 255) - 1
         self._metrics_lut = None          # fp32[256] on the device: byte -> float32(u) / float32(255), uploaded once
+        # tools/fp16_headroom.py sets this to a `range.RangeProbe`: the operators then record `range_stats` of the activation
+        # tensor they wrote (eager only; nothing they compute changes)
+        self.range_probe = None
 
     # ---- helpers
     def bind_thread(self) -> None:
@@ -341,6 +359,10 @@ class Hip:
         e1.record()
         self.kernel_profile.append((e0, e1, family, float(flops), float(nbytes)))
         return r
+
+    def _probe(self, family: str, entry: str, t, rows=None, cols=None, ld=None):
+        """Hand the activation tensor an operator of `family` just wrote (through `entry`) to the range probe."""
+        self.range_probe.record(self, family, t, rows=rows, cols=cols, ld=ld, entry=entry)
 
     def _ck(self, rc: int, what: str):
         if rc != 0:
@@ -395,6 +417,8 @@ class Hip:
             a.splitk, a.workspace = splitk, self._splitk_ws.data_ptr()
         if self.gemm_profile is None:
             self._ck(self.lib.wiw_gemm_bf16(self._stream(), C.byref(a)), "wiw_gemm_bf16")
+            if self.range_probe is not None:
+                self._probe("gemm", "wiw_gemm_bf16", out, M, n_out if epilogue & EPI_GEGLU else N, a.ldo)
             return out
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
@@ -404,6 +428,8 @@ class Hip:
         self.gemm_profile.append((e0, e1, 2.0 * M * N * K, mode,
                                   (M, N, K, epilogue | (PROF_RES1 if res1 is not None else 0) | (PROF_RES2 if res2 is not None else 0)
                                    | (a.epilogue & (EPI_RES1_F32 | EPI_RES2_F32)))))
+        if self.range_probe is not None:
+            self._probe("gemm", "wiw_gemm_bf16", out, M, n_out if epilogue & EPI_GEGLU else N, a.ldo)
         return out
 
     def attn_spatial(self, QK, ldqk, k_col_off, Vt, ldvt, O, ldo, frames, S, heads, scale, lse=None):
@@ -414,10 +440,14 @@ class Hip:
             self._timed("attn_spatial", 4.0 * frames * heads * S * S * 64, 8.0 * frames * S * heads * 64, lambda: self._ck(
                 self.lib.wiw_attn_spatial_lse_bf16(self._stream(), _p(QK), ldqk, k_col_off, _p(Vt), ldvt, _p(O), ldo, frames, S,
                                                    heads, scale, self.zeros.data_ptr(), _p(lse)), "wiw_attn_spatial_lse_bf16"))
+            if self.range_probe is not None:
+                self._probe("attn_spatial", "wiw_attn_spatial_lse_bf16", O, frames * S, heads * 64, ldo)
             return O
         self._timed("attn_spatial", 4.0 * frames * heads * S * S * 64, 8.0 * frames * S * heads * 64, lambda: self._ck(
             self.lib.wiw_attn_spatial_bf16(self._stream(), _p(QK), ldqk, k_col_off, _p(Vt), ldvt, _p(O), ldo,
                                            frames, S, heads, scale, self.zeros.data_ptr()), "wiw_attn_spatial_bf16"))
+        if self.range_probe is not None:
+            self._probe("attn_spatial", "wiw_attn_spatial_bf16", O, frames * S, heads * 64, ldo)
         return O
 
     def attn_spatial_ps(self, QK, ldqk, k_col_off, Vt, ldvt, O, ldo, frames, S, heads):
@@ -425,6 +455,8 @@ class Hip:
         self._timed("attn_spatial", 4.0 * frames * heads * S * S * 64, 8.0 * frames * S * heads * 64, lambda: self._ck(
             self.lib.wiw_attn_spatial_ps_bf16(self._stream(), _p(QK), ldqk, k_col_off, _p(Vt), ldvt, _p(O), ldo,
                                               frames, S, heads, self.zeros.data_ptr()), "wiw_attn_spatial_ps_bf16"))
+        if self.range_probe is not None:
+            self._probe("attn_spatial", "wiw_attn_spatial_ps_bf16", O, frames * S, heads * 64, ldo)
         return O
 
     def attn_spatial_ps_padded(self, QK, ldqk, k_col_off, Vt, ldvt, O, ldo, frames, S, Sv, heads):
@@ -432,12 +464,16 @@ class Hip:
         self._timed("attn_spatial", 4.0 * frames * heads * S * S * 64, 8.0 * frames * S * heads * 64, lambda: self._ck(
             self.lib.wiw_attn_spatial_ps_padded_bf16(self._stream(), _p(QK), ldqk, k_col_off, _p(Vt), ldvt, _p(O), ldo,
                                                      frames, S, Sv, heads, self.zeros.data_ptr()), "wiw_attn_spatial_ps_padded_bf16"))
+        if self.range_probe is not None:
+            self._probe("attn_spatial", "wiw_attn_spatial_ps_padded_bf16", O, frames * S, heads * 64, ldo)
         return O
 
     def attn_temporal(self, QKV, ldqkv, O, ldo, batch, T, S, heads, scale):
         self._timed("attn_temporal", 4.0 * batch * S * heads * T * T * 64, 8.0 * batch * T * S * heads * 64, lambda: self._ck(
             self.lib.wiw_attn_temporal_bf16(self._stream(), _p(QKV), ldqkv, _p(O), ldo, batch, T, S, heads, scale),
             "wiw_attn_temporal_bf16"))
+        if self.range_probe is not None:
+            self._probe("attn_temporal", "wiw_attn_temporal_bf16", O, batch * T * S, heads * 64, ldo)
         return O
 
     def temporal_attn_block(self, X, Wqkv, fold, O, ldo, batch, T, S, heads, eps, scale):
@@ -450,6 +486,8 @@ class Hip:
             self.lib.wiw_temporal_attn_block_bf16(self._stream(), _p(X), _p(Wqkv), _p(fold), _p(O), ldo, batch, T, S,
                                                   heads, eps, scale, self.zeros.data_ptr()),
             "wiw_temporal_attn_block_bf16"))
+        if self.range_probe is not None:
+            self._probe("temporal_block", "wiw_temporal_attn_block_bf16", O, M, Cn, ldo)
         return O
 
     def attn_temporal32(self, QKV, ldqkv, O, ldo, batch, T, S, heads, scale):
@@ -457,6 +495,8 @@ class Hip:
         self._timed("attn_temporal", 4.0 * batch * S * heads * T * T * 64, 8.0 * batch * T * S * heads * 64, lambda: self._ck(
             self.lib.wiw_attn_temporal32_bf16(self._stream(), _p(QKV), ldqkv, _p(O), ldo, batch, T, S, heads, scale),
             "wiw_attn_temporal32_bf16"))
+        if self.range_probe is not None:
+            self._probe("attn_temporal", "wiw_attn_temporal32_bf16", O, batch * T * S, heads * 64, ldo)
         return O
 
     def temporal_attn_block32(self, X, Wqkv, fold, O, ldo, batch, T, S, heads, eps, scale):
@@ -467,6 +507,8 @@ class Hip:
             self.lib.wiw_temporal_attn_block32_bf16(self._stream(), _p(X), _p(Wqkv), _p(fold), _p(O), ldo, batch, T, S,
                                                     heads, eps, scale),
             "wiw_temporal_attn_block32_bf16"))
+        if self.range_probe is not None:
+            self._probe("temporal_block", "wiw_temporal_attn_block32_bf16", O, M, Cn, ldo)
         return O
 
     def ffn_geglu(self, X, W1, b1, W2, b2, out, M, *, ldx=FFN_C, rowvec=None, rowvec_ld=0, rows_per_vec=1, res1=None, ldr1=0,
@@ -502,6 +544,12 @@ class Hip:
                                                  _p(out), ldo, M, FFN_C, FFN_HIDDEN, 1 if ln else 0, ln_eps),
                      "wiw_ffn_geglu_bf16")
         self._timed("ffn_fused", flops, nbytes, launch)
+        if self.range_probe is not None:
+            entry = ("wiw_ffn_geglu_f32stream2" if (f32 & 8) or out16 is not None else "wiw_ffn_geglu_f32stream" if f32
+                     else "wiw_ffn_geglu_bf16")
+            self._probe("ffn_fused", entry, out, M, FFN_C, ldo)
+            if out16 is not None:
+                self._probe("ffn_fused", entry, out16, M, FFN_C, FFN_C)
         return out
 
     def ffn32_geglu(self, X, W1, b1, W2, b2, out, M, *, ldx=FFN_C, rowvec=None, rowvec_ld=0, rows_per_vec=1, res1=None, ldr1=0,
@@ -517,6 +565,8 @@ class Hip:
             self.lib.wiw_ffn32_geglu(self._stream(), _p(X), ldx, _p(W1), _p(b1), _p(W2), _p(b2), _p(rowvec), rowvec_ld, rows_per_vec,
                                      _p(res1), ldr1, beta1, _p(res2), ldr2, beta2, alpha, _p(out), ldo, M, FFN_C, FFN_HIDDEN,
                                      1 if ln else 0, ln_eps, f32), "wiw_ffn32_geglu"))
+        if self.range_probe is not None:
+            self._probe("ffn_fused", "wiw_ffn32_geglu", out, M, FFN_C, ldo)
         return out
 
     def cross_attn_fewkeys(self, Q, ldq, K, V, O, ldo, rows, rows_per_item, heads, P, scale):
@@ -527,6 +577,8 @@ class Hip:
         self._timed("attn_cross", 4.0 * rows * P * C_, 4.0 * rows * C_, lambda: self._ck(
             self.lib.wiw_cross_attn_fewkeys_bf16(self._stream(), _p(Q), ldq, _p(K), _p(V), _p(O), ldo, rows, rows_per_item, heads, P,
                                                  scale), "wiw_cross_attn_fewkeys_bf16"))
+        if self.range_probe is not None:
+            self._probe("attn_cross", "wiw_cross_attn_fewkeys_bf16", O, rows, C_, ldo)
         return O
 
     def cross_attn_fewkeys_backward(self, Q, ldq, K, V, dO, lddo, rows, rows_per_item, heads, P, scale, dQ=None, lddq=None):
@@ -552,6 +604,8 @@ class Hip:
         self._timed("attn_small", 4.0 * seqs * heads * S * S * head_dim, 8.0 * seqs * S * heads * head_dim, lambda: self._ck(
             self.lib.wiw_attn_small_bf16(self._stream(), _p(QK), ldqk, k_col_off, _p(Vt), ldvt, _p(O), ldo, seqs, S, Sp,
                                          heads, head_dim, scale), "wiw_attn_small_bf16"))
+        if self.range_probe is not None:
+            self._probe("attn_small", "wiw_attn_small_bf16", O, seqs * Sp, heads * head_dim, ldo)
         return O
 
     def clip_preprocess(self, img, B, H0, W0, out_size, patch, taps_x, taps_y, mean, inv_std, tmp, A, rows_per_image, ldA):
@@ -559,6 +613,8 @@ class Hip:
         self._ck(self.lib.wiw_clip_preprocess(self._stream(), _p(img), B, H0, W0, out_size, patch, fa(taps_x), len(taps_x),
                                               fa(taps_y), len(taps_y), fa(mean), fa(inv_std), _p(tmp), _p(A), rows_per_image,
                                               ldA), "wiw_clip_preprocess")
+        if self.range_probe is not None:
+            self._probe("clip_preprocess", "wiw_clip_preprocess", A, B * rows_per_image, ldA, ldA)
         return A
 
     @staticmethod
@@ -625,6 +681,8 @@ class Hip:
             self._timed("groupnorm", 0.0, 4.0 * rows * Ct, lambda: self._ck(self.lib.wiw_groupnorm_onepass(
                 s, _p(X1), C1, _p(X2), C2, rows, rows_per_unit, _p(gamma), _p(beta), eps, 1 if silu else 0, out.data_ptr()),
                 "wiw_groupnorm_onepass"))
+            if self.range_probe is not None:
+                self._probe("groupnorm", "wiw_groupnorm_onepass", out, rows, Ct, Ct)
             return out
         rpb = self.gn_rows_per_block(rows_per_unit, clip)
         stats, scratch, cnt = self._gn_buffers(rows, rows_per_unit, rpb)
@@ -647,6 +705,11 @@ class Hip:
 
         # algorithmic bytes: the input is read twice (statistics, apply) and the output written once (bf16)
         self._timed("groupnorm", 0.0, ((10.0 if f32in else 6.0) + (2.0 if raw16 is not None else 0.0)) * rows * Ct, launch)
+        if self.range_probe is not None:
+            entry = "wiw_groupnorm_apply_stats_f32in" if f32in else "wiw_groupnorm_apply_stats"
+            self._probe("groupnorm", entry, out, rows, Ct, Ct)
+            if raw16 is not None:
+                self._probe("groupnorm", entry, raw16, rows, Ct, Ct)
         return out
 
     def groupnorm_unfused(self, X1, C1, X2, C2, rows, rows_per_unit, gamma, beta, eps, silu, out=None, clip=False):
@@ -676,10 +739,16 @@ class Hip:
             self._timed("layernorm", 0.0, 6.0 * rows * Cn, lambda: self._ck(
                 self.lib.wiw_layernorm_f32in(self._stream(), _p(X), rows, Cn, _p(gamma), _p(beta), eps, out.data_ptr()),
                 "wiw_layernorm_f32in"))
+            if self.range_probe is not None:
+                self._probe("layernorm", "wiw_layernorm_f32in", out, rows, Cn, Cn)
             return out
         self._timed("layernorm", 0.0, (6.0 if sum_out is not None else 4.0) * rows * Cn, lambda: self._ck(
             self.lib.wiw_layernorm_bf16(self._stream(), _p(X), rows, Cn, _p(gamma), _p(beta), eps, _p(addvec),
                                         addvec_ld, rows_per_vec, _p(sum_out), out.data_ptr()), "wiw_layernorm_bf16"))
+        if self.range_probe is not None:
+            self._probe("layernorm", "wiw_layernorm_bf16", out, rows, Cn, Cn)
+            if sum_out is not None:
+                self._probe("layernorm", "wiw_layernorm_bf16", sum_out, rows, Cn, Cn)
         return out
 
     def cast16(self, X, out=None):
@@ -689,6 +758,8 @@ class Hip:
             out = torch.empty(X.shape, dtype=self.dtype, device=self.device)
         self._timed("cast16", 0.0, 6.0 * X.numel(), lambda: self._ck(
             self.lib.wiw_cast_f32_to_16(self._stream(), _p(X), X.numel(), out.data_ptr()), "wiw_cast_f32_to_16"))
+        if self.range_probe is not None:
+            self._probe("cast16", "wiw_cast_f32_to_16", out)
         return out
 
     def calibrate_box(self, target_ms: float = 50.0, sustain_s: float = 1.0):
@@ -941,6 +1012,43 @@ class Hip:
                  "wiw_frame_metrics")
         return out
 
+    # ---- value-range statistics (csrc/range.hip, include/wiw_range.h)
+    def range_stats(self, t, rows=None, cols=None, ld=None, rows_per_segment=None, f32=None, hot=None, tiny=None, hist=False):
+        """Per-segment range statistics of the device tensor `t` read as rows x cols with leading dimension ld (elements):
+        -> (stats, hist): uint8 (segments, 48) holding one WiwRangeStats per segment, and int64 (segments, 64) holding the bits
+        of the uint64 bin counts or None; both on the device and NOT read here (no synchronisation; `range.stats_records` turns
+        them into records after the caller's own).  Defaults: t is 2-D (its shape and row stride; unit stride along the columns) or contiguous and taken as one
+        row; one segment; f32 from t.dtype (the library's 16-bit type or fp32); hot = half the type's largest finite value and
+        tiny = its smallest normal (`range.thresholds`).  Segments are consecutive groups of rows_per_segment rows."""
+        from .range import thresholds
+        assert t.device == self.device
+        if rows is None:
+            if t.dim() == 2 and (t.stride(1) == 1 or t.shape[1] == 1):
+                rows, cols = t.shape
+                ld = ld if ld is not None else (t.stride(0) if rows > 1 else cols)
+            else:
+                assert t.is_contiguous(), "range_stats: give rows / cols / ld for a strided tensor"
+                rows, cols = 1, t.numel()
+        ld = cols if ld is None else ld
+        if cols >= 1 << 31:
+            raise ValueError(f"range_stats: {cols} columns; hand a tensor this long over as rows x cols (cols is a C int)")
+        rows_per_segment = rows if rows_per_segment is None else rows_per_segment
+        if f32 is None:
+            assert t.dtype in (torch.float32, self.dtype), t.dtype
+            f32 = t.dtype == torch.float32
+        d_hot, d_tiny = thresholds(torch.float32 if f32 else self.dtype)
+        hot, tiny = d_hot if hot is None else hot, d_tiny if tiny is None else tiny
+        nbytes = self.lib.wiw_range_stats_partials(rows, cols, rows_per_segment, int(bool(hist)))
+        if nbytes <= 0:
+            raise ValueError(f"range_stats: rows {rows}, cols {cols}, rows_per_segment {rows_per_segment}")
+        segments = rows // rows_per_segment
+        partials = torch.empty(nbytes // 8, dtype=torch.int64, device=self.device)
+        stats = torch.empty(segments, C.sizeof(WiwRangeStats), dtype=torch.uint8, device=self.device)
+        bins = torch.empty(segments, RANGE_BINS, dtype=torch.int64, device=self.device) if hist else None   # the bits of uint64
+        self._ck(self.lib.wiw_range_stats(self._stream(), _p(t), int(bool(f32)), rows, cols, ld, rows_per_segment, hot, tiny,
+                                          _p(partials), _p(stats), _p(bins)), "wiw_range_stats")
+        return stats, bins
+
     # ---- backward building blocks (row f2; csrc/train.hip)
     def colsum(self, X, rows, Cn, parts=None, units=1):
         """fp32 column sums of X [rows, Cn] (16-bit or fp32), fixed summation order.  units == 1: -> [Cn].  units > 1: X is
@@ -1138,14 +1246,20 @@ class Hip:
     def softmax_rows(self, X, ldx, rows, cols, P, ldp):
         self._ck(self.lib.wiw_softmax_rows_f32_bf16(self._stream(), _p(X), ldx, rows, cols, _p(P), ldp),
                  "wiw_softmax_rows_f32_bf16")
+        if self.range_probe is not None:
+            self._probe("softmax_rows", "wiw_softmax_rows_f32_bf16", P, rows, cols, ldp)
         return P
 
     def vae_time_conv_out(self, Y, ldy, weight, bias, frames, T, HW, out):
         self._ck(self.lib.wiw_vae_time_conv_out(self._stream(), _p(Y), ldy, _p(weight), _p(bias), frames, T, HW,
                                                 _p(out)), "wiw_vae_time_conv_out")
+        if self.range_probe is not None:
+            self._probe("vae_time_conv_out", "wiw_vae_time_conv_out", out)
         return out
 
     def nchw_to_nhwc(self, X, frames, Cin, HW, scale, Cpad, out):
         self._ck(self.lib.wiw_nchw_f32_to_nhwc_bf16(self._stream(), _p(X), frames, Cin, HW, scale, Cpad, _p(out)),
                  "wiw_nchw_f32_to_nhwc_bf16")
+        if self.range_probe is not None:
+            self._probe("nchw_to_nhwc", "wiw_nchw_f32_to_nhwc_bf16", out, frames * HW, Cpad, Cpad)
         return out

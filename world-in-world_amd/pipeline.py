@@ -147,6 +147,9 @@ class GraphedForward:
         self.emb = torch.zeros((cond.Bc * cfg.num_frames, cfg.time_embed_dim), dtype=unet.dtype, device=unet.device)
         hip = unet.hip
         assert hip.gemm_profile is None and hip.kernel_profile is None, "per-launch events cannot be recorded inside a capture"
+        if hip.range_probe is not None:      # its records would be made once, at capture, and read before any replay
+            raise RuntimeError("range probe: set while a forward is being captured; probe an eager forward "
+                               "(SVDDenoiser(use_graph=False), --no-hip_graph)")
         # ONE warm-up stream per Hip for every capture of the process: GroupNorm counter rows are keyed by stream
         # (Hip._gn_buffers), and a fresh torch.cuda.Stream per capture walked torch's 32-stream pool until the rows ran out —
         # a server seeing many (candidates, h, w) shapes then fell back to the eager loop for good
@@ -309,8 +312,9 @@ class SVDDenoiser:
             s, sn = float(sig[i]), float(sig[i + 1])
             self.hip.prep_unet_input(lat, img, B, T, hw, s, CIN_PAD, x_in)
             emb = self.unet.time_embedding(float(ts[i]), cond)
-            # (a step that carries per-launch events — bench.py — runs eagerly on the same static buffers)
-            replay = gf is not None and self.hip.gemm_profile is None and self.hip.kernel_profile is None
+            # (a step that carries per-launch events — bench.py — or a range probe runs eagerly on the same static buffers)
+            replay = (gf is not None and self.hip.gemm_profile is None and self.hip.kernel_profile is None
+                      and self.hip.range_probe is None)
             t0 = time.perf_counter()
             v = gf(emb) if replay else self.unet.forward(x_in, emb, cond, h, w)
             hl = self.host_launch["graph" if replay else "eager"]

@@ -21,6 +21,7 @@ Two transports:
 from __future__ import annotations
 
 import argparse
+import inspect
 import logging
 import os
 import socket
@@ -30,6 +31,7 @@ from typing import Callable, Optional, Protocol
 
 import numpy as np
 
+from ..range import reference_stats, stats_records
 from ..resample import MAX_TAPS, supported
 from . import plumbing as P
 from .protocol import DONE, read_framed, read_pickled, write_framed, write_pickled
@@ -61,16 +63,44 @@ class Frontend(Protocol):
     #       the PIL resize to out_size = (ow, oh); the bytes of `decode` + `frames_to_pil` + `images_to_tensor`.
 
 
+GUARD_MODES = ("off", "error", "fallback")
+
+
+class NonFiniteOutput(RuntimeError):
+    """A request produced NaN or inf (`SVDWorker(finite_guard=...)`).  indices: the bad candidates of the request, in order;
+    save_dirs: theirs; stage: "latents" if one of them was already bad when the denoising loop returned, else "frames" (the
+    decoder made it); stages: the same per bad candidate; counts: per bad candidate {"latents": (n_nan, n_inf), "frames": ...}."""
+
+    def __init__(self, indices, save_dirs, stages, counts, where: str = ""):
+        self.indices, self.save_dirs, self.stages, self.counts = list(indices), list(save_dirs), list(stages), list(counts)
+        self.stage = "latents" if "latents" in self.stages else "frames"
+        super().__init__(f"non-finite output{where}: candidates {self.indices} (first bad at {self.stages}), "
+                         f"(NaN, inf) counts {self.counts}, save_dirs {self.save_dirs}")
+
+
 class SVDWorker:
     def __init__(self, denoise_fn: Callable[..., "np.ndarray"], frontend: Frontend, *, width=1024, height=576,
                  out_width=480, out_height=480, num_frames=14, num_inference_steps=30, seed=1,
                  world_model_name=P.WORLD_MODEL_NAME, noise_fn: Optional[Callable] = None, task_type: str = "navigation",
-                 device_resize: bool = False):
+                 device_resize: bool = False, finite_guard: str = "off", fallback: Optional["SVDWorker"] = None):
         """device_resize: both image resizes of a request (LANCZOS in, BICUBIC out) run behind the frontend's
         `encode_uint8` / `decode_resized_uint8` (PIL's integer arithmetic on the device: the same bytes) instead of in PIL on
         the host; taken with a frontend that has both methods (otherwise one logged line and the host path).  A geometry those
         kernels refuse (more than 64 taps: a side shrunk by more than ~10x) is served by the host path for that request.
-        False: nothing differs from the host path."""
+        False: nothing differs from the host path.
+
+        finite_guard: "off" (default: nothing is checked and nothing more is launched); "error": every candidate's fp32
+        latents (as the denoising loop returns them) and fp32 frames (as the decoder holds them, before quantisation) are
+        counted for NaN / inf (`Hip.range_stats`, one segment per candidate; `range.reference_stats` for host arrays), the
+        counts are read after the frames' own copy to the host, and a bad candidate raises `NonFiniteOutput` before anything
+        is written under a save_dir; "fallback": the bad candidates are rendered again by `fallback` — a second SVDWorker of
+        the same geometry on a wider-range chain (bf16: fp32's exponent range; `serve_worker.build_worker` builds it) — from
+        the same images, action rows and the same two noise draws (kept until the verdict; the generator is not advanced
+        again), and its frames take their places; if those are not finite either, `NonFiniteOutput`."""
+        if finite_guard not in GUARD_MODES:
+            raise ValueError(f"finite_guard must be one of {GUARD_MODES}, got {finite_guard!r}")
+        if finite_guard == "fallback" and fallback is None:
+            raise ValueError("finite_guard='fallback' needs the fallback worker")
         self.denoise_fn = denoise_fn
         self.frontend = frontend
         self.device_resize = bool(device_resize) and hasattr(frontend, "encode_uint8") and hasattr(frontend, "decode_resized_uint8")
@@ -86,6 +116,26 @@ class SVDWorker:
         self._rng = np.random.Generator(np.random.Philox(seed))
         self.noise_fn = noise_fn or (lambda shape: self._rng.standard_normal(shape, dtype=np.float32))
         self.bind_thread: Optional[Callable[[], None]] = None   # set by the launcher: per-thread HIP device binding
+        self.finite_guard = finite_guard
+        self.fallback = fallback
+        # which of the frontend's decoders report on their fp32 frames through `range_out` (looked up once)
+        self._takes_range_out = {name: "range_out" in inspect.signature(getattr(frontend, name)).parameters
+                                 for name in ("decode", "decode_uint8", "decode_resized_uint8") if hasattr(frontend, name)}
+        self._guard_lock = threading.Lock()
+        self._guard = {"requests": 0, "candidates_checked": 0, "bad_latents": 0, "bad_frames": 0, "re_served": 0, "failed": 0}
+
+    def guard_status(self) -> dict:
+        """Counters of the finite guard since start-up: requests and candidates checked, candidates found bad by the stage
+        that first showed it, candidates served again by the fallback chain, candidates that failed (an error was raised).
+        They count CALLS of the worker: a merged batch that fails behind a `Coalescer` and is served again request by request
+        counts in both attempts."""
+        with self._guard_lock:
+            return dict(self._guard, mode=self.finite_guard)
+
+    def _count(self, **inc) -> None:
+        with self._guard_lock:
+            for k, v in inc.items():
+                self._guard[k] += v
 
     def __call__(self, request: dict) -> dict:
         """do_some_tasks (eval_inference.py:313-349)."""
@@ -93,38 +143,125 @@ class SVDWorker:
             self.bind_thread()
         b_action, save_dirs, return_objects, images = P.parse_request(request, self.world_model_name)
         b_action = P.check_b_action(b_action, self.num_frames, self.task_type)
-        B = len(images)
+        device_path = False
         if self.device_resize:
-            if self._device_resize_serves(images):
-                return self._call_device_resize(images, b_action, save_dirs, return_objects)
-            log.warning("device_resize: a resize of this request needs more than %d taps per sample; served by the host (PIL) path",
-                        MAX_TAPS)
-        x = np.stack([P.preprocess_image(im, self.width, self.height) for im in images])
-        # CLIP sees the image at its ORIGINAL size (pipeline:192-199); only the VAE branch is resized (pipeline:521)
-        clip_images = None
-        if any(im.size != (self.width, self.height) for im in images):
-            clip_images = [P.image_to_array(im) for im in images]
-        img_noise = self.noise_fn(x.shape)                                   # draw 1 (pipeline:522)
-        if clip_images is None:
-            image_latents, image_embeddings = self.frontend.encode(x, img_noise, 0.02)
+            device_path = self._device_resize_serves(images)
+            if not device_path:
+                log.warning("device_resize: a resize of this request needs more than %d taps per sample; served by the host (PIL) path",
+                            MAX_TAPS)
+        check = self.finite_guard != "off"
+        video, draws, verdict = self._render(images, b_action, device_path, None, check)
+        if check:
+            video = self._judge(video, draws, verdict, images, b_action, list(save_dirs), device_path)
+        build = P.build_response_u8 if device_path else P.build_response
+        out = build(video, b_action, list(save_dirs), return_objects)
+        P.check_outputdict(out)
+        return out
+
+    def _render(self, images, b_action, device_path: bool, draws, check: bool):
+        """Images + actions -> the response's video ((B, T, 3, oh, ow): float32 in [0, 1] from the host resize, uint8 from the
+        device resize).  draws: None — the two noise draws come from `noise_fn`, in the reference's order — or the
+        (image noise, latent noise) to use instead (the fallback chain replays the first chain's).  check: also count NaN / inf
+        per candidate.  -> (video, (image noise, latent noise), verdict: per candidate {"latents": (n_nan, n_inf), "frames": ...}
+        or None)."""
+        B = len(images)
+        if device_path:
+            images_u8 = [P.image_to_u8_planes(im) for im in images]
+            img_noise = self.noise_fn((B, 3, self.height, self.width)) if draws is None else draws[0]   # draw 1 (pipeline:522)
+            image_latents, image_embeddings = self.frontend.encode_uint8(images_u8, img_noise, 0.02, (self.width, self.height))
         else:
-            image_latents, image_embeddings = self.frontend.encode(x, img_noise, 0.02, clip_images=clip_images)
+            x = np.stack([P.preprocess_image(im, self.width, self.height) for im in images])
+            # CLIP sees the image at its ORIGINAL size (pipeline:192-199); only the VAE branch is resized (pipeline:521)
+            clip_images = None
+            if any(im.size != (self.width, self.height) for im in images):
+                clip_images = [P.image_to_array(im) for im in images]
+            img_noise = self.noise_fn(x.shape) if draws is None else draws[0]                           # draw 1 (pipeline:522)
+            if clip_images is None:
+                image_latents, image_embeddings = self.frontend.encode(x, img_noise, 0.02)
+            else:
+                image_latents, image_embeddings = self.frontend.encode(x, img_noise, 0.02, clip_images=clip_images)
         h, w = image_latents.shape[-2:]
-        lat_noise = self.noise_fn((B, self.num_frames, 4, h, w))             # draw 2 (pipeline:765)
+        lat_noise = self.noise_fn((B, self.num_frames, 4, h, w)) if draws is None else draws[1]         # draw 2 (pipeline:765)
         latents = self.denoise_fn(image_latents, image_embeddings, lat_noise, b_action,
                                   num_steps=self.num_inference_steps, fps=7, motion_bucket_id=127,
                                   noise_aug_strength=0.02)
-        if hasattr(self.frontend, "decode_uint8"):    # frame quantisation on the device (same arithmetic, same bytes);
+        # the guard's first check point: launched here, read below after the frames have come to the host
+        lat_stats = self._launch_latent_stats(latents) if check else None
+        frame_stats: Optional[list] = [] if check else None
+
+        def kw(decode):          # the guard's second check point: the decoder reports on the fp32 frames it holds
+            if not check:
+                return {}
+            if not self._takes_range_out[decode.__name__]:
+                if decode.__name__ != "decode":
+                    raise RuntimeError(f"finite_guard: the frontend's {decode.__name__} takes no range_out argument")
+                return {}          # `decode` hands the fp32 frames over: they are counted below
+            return {"range_out": frame_stats}
+        if device_path:
+            video = self.frontend.decode_resized_uint8(latents, self.out_size, "bicubic", **kw(self.frontend.decode_resized_uint8))
+        elif hasattr(self.frontend, "decode_uint8"):    # frame quantisation on the device (same arithmetic, same bytes);
             # `latents` may be a device tensor: nothing crosses PCIe between the loop and the decoder
-            clips = [[P.Image.fromarray(f) for f in clip] for clip in self.frontend.decode_uint8(latents)]
+            clips = [[P.Image.fromarray(f) for f in clip]
+                     for clip in self.frontend.decode_uint8(latents, **kw(self.frontend.decode_uint8))]
+            video = P.images_to_tensor(clips, save_size=self.out_size)
         else:
             lat = np.asarray(latents.cpu() if hasattr(latents, "cpu") else latents, dtype=np.float32)
-            frames = self.frontend.decode(lat)         # (B,T,3,H,W) in [-1,1]
+            frames = self.frontend.decode(lat, **kw(self.frontend.decode))         # (B,T,3,H,W) in [-1,1]
+            if check and not frame_stats:
+                frame_stats.extend(reference_stats(np.asarray(frames), rows_per_segment=1, hist=False))
             clips = [P.frames_to_pil(f) for f in frames]
-        video = P.images_to_tensor(clips, save_size=self.out_size)
-        out = P.build_response(video, b_action, list(save_dirs), return_objects)
-        P.check_outputdict(out)
-        return out
+            video = P.images_to_tensor(clips, save_size=self.out_size)
+        verdict = None
+        if check:
+            lat_recs = lat_stats() if callable(lat_stats) else lat_stats
+            assert len(lat_recs) == B and len(frame_stats) == B, "the guard needs one record per candidate from both stages"
+            verdict = [{"latents": (l["n_nan"], l["n_inf"]), "frames": (f["n_nan"], f["n_inf"])}
+                       for l, f in zip(lat_recs, frame_stats)]
+        return video, (img_noise, lat_noise), verdict
+
+    def _launch_latent_stats(self, latents):
+        """Per-candidate statistics of the latents (B, T, 4, h, w): records, or — for a device tensor — a callable that reads
+        the device buffers (call it after the synchronisation the frames' copy makes anyway)."""
+        if getattr(latents, "is_cuda", False):
+            if not hasattr(self.frontend, "candidate_stats"):
+                raise RuntimeError("finite_guard: device latents need a frontend with candidate_stats (vae.HIPFrontend)")
+            buf = self.frontend.candidate_stats(latents)
+            return lambda: stats_records(buf)
+        lat = np.asarray(latents.cpu() if hasattr(latents, "cpu") else latents, dtype=np.float32)
+        return reference_stats(lat, rows_per_segment=1, hist=False)
+
+    @staticmethod
+    def _bad(verdict):
+        """-> [(candidate, first bad stage)] of a verdict."""
+        return [(i, "latents" if sum(v["latents"]) else "frames") for i, v in enumerate(verdict) if sum(v["latents"]) + sum(v["frames"])]
+
+    def _judge(self, video, draws, verdict, images, b_action, save_dirs, device_path: bool):
+        """The verdict on one rendered request, before anything of it is written: -> the video to answer with, or raises."""
+        bad = self._bad(verdict)
+        self._count(requests=1, candidates_checked=len(verdict), bad_latents=sum(s == "latents" for _, s in bad),
+                    bad_frames=sum(s == "frames" for _, s in bad))
+        if not bad:
+            return video
+        idx = [i for i, _ in bad]
+        err = NonFiniteOutput(idx, [save_dirs[i] for i in idx], [s for _, s in bad], [verdict[i] for i in idx])
+        if self.finite_guard == "error":
+            self._count(failed=len(idx))
+            log.error("finite_guard: %s; the request fails", err)
+            raise err
+        fb_video, _, fb_verdict = self.fallback._render([images[i] for i in idx], b_action[idx], device_path,
+                                                        (draws[0][idx], draws[1][idx]), True)
+        fb_bad = self.fallback._bad(fb_verdict)
+        if fb_bad:
+            self._count(failed=len(idx))
+            err = NonFiniteOutput([idx[k] for k, _ in fb_bad], [save_dirs[idx[k]] for k, _ in fb_bad], [s for _, s in fb_bad],
+                                  [fb_verdict[k] for k, _ in fb_bad], where=" of the fallback chain too")
+            log.error("finite_guard: %s; the request fails", err)
+            raise err
+        self._count(re_served=len(idx))
+        log.warning("finite_guard: %s; served again by the fallback chain", err)
+        video = np.array(video)                  # the good candidates' values, untouched
+        video[idx] = np.asarray(fb_video, dtype=video.dtype)
+        return video
 
     def _device_resize_serves(self, images) -> bool:
         """Whether the resampling kernels take every resize of this request (`resample.supported`: at most 64 taps a sample)."""
@@ -133,22 +270,6 @@ class SVDWorker:
         for im in images:
             sides += [(im.size[0], self.width, "lanczos"), (im.size[1], self.height, "lanczos")]
         return all(supported(*s) for s in set(sides))
-
-    def _call_device_resize(self, images, b_action, save_dirs, return_objects) -> dict:
-        """`__call__` with both resizes behind the frontend: same draws (order and shapes), same denoise call, same bytes."""
-        B = len(images)
-        images_u8 = [P.image_to_u8_planes(im) for im in images]
-        img_noise = self.noise_fn((B, 3, self.height, self.width))           # draw 1 (pipeline:522)
-        image_latents, image_embeddings = self.frontend.encode_uint8(images_u8, img_noise, 0.02, (self.width, self.height))
-        h, w = image_latents.shape[-2:]
-        lat_noise = self.noise_fn((B, self.num_frames, 4, h, w))             # draw 2 (pipeline:765)
-        latents = self.denoise_fn(image_latents, image_embeddings, lat_noise, b_action,
-                                  num_steps=self.num_inference_steps, fps=7, motion_bucket_id=127,
-                                  noise_aug_strength=0.02)
-        video_u8 = self.frontend.decode_resized_uint8(latents, self.out_size, "bicubic")
-        out = P.build_response_u8(video_u8, b_action, list(save_dirs), return_objects)
-        P.check_outputdict(out)
-        return out
 
 
 # ------------------------------------------------------------------------------------------------
@@ -396,6 +517,11 @@ def build_arg_parser() -> argparse.ArgumentParser:
                     help="resize the conditioning image (LANCZOS) and the decoded frames (BICUBIC) on the GPU with PIL's integer "
                          "arithmetic (csrc/resample.hip: the same bytes) instead of in PIL on the host; the frames leave the GPU once, "
                          "already (T, 3, out_height, out_width) uint8.  OFF by default")
+    ap.add_argument("--finite_guard", type=str, default="off", choices=list(GUARD_MODES),
+                    help="count NaN / inf in every candidate's fp32 latents and fp32 frames on the device (csrc/range.hip; read after "
+                         "the frames' own copy to the host: no extra synchronisation).  error: a bad candidate fails its request "
+                         "(NonFiniteOutput) before anything is written; fallback: the bad candidates are served again by a second, "
+                         "bfloat16 chain built at start-up (the same draws; needs --weight_dtype float16).  OFF by default")
     ap.add_argument("--batch_size", type=int, default=0)
     ap.add_argument("--coalesce_candidates", type=int, default=0,
                     help="> 0: batch requests of different clients into one GPU call of up to this many candidates")
@@ -430,7 +556,8 @@ def validate_args(args) -> None:
     embedder width the task cannot produce (navigation: one channel per frame, get_action_ids micro_cond; manipulation: 10 =
     [norm_xyz | r6 | norm_grip] or num_frames + 9, its positional form — utils/svd_utils.py:418-457, 499-567); an output
     --width / --height that is not a multiple of 64 (the 1/8 latent goes through three 2x downsamples of the UNet).  Any
-    multiple of 64 is served: the spatial attention takes every token count (e.g. 7x7 and 14x14 at 448x448)."""
+    multiple of 64 is served: the spatial attention takes every token count (e.g. 7x7 and 14x14 at 448x448);
+    --finite_guard fallback on a bfloat16 worker (the fallback chain is the bfloat16 one)."""
     for flag in ("width", "height"):
         v = getattr(args, flag, None)
         if v is not None and (v <= 0 or v % 64 != 0):
@@ -445,6 +572,9 @@ def validate_args(args) -> None:
                          f"pipeline:291-302; chunking changes the temporal convolutions) and the decoder's widest activation, "
                          f"{args.num_frames} x {h_} x {w_} rows of {VAE_WIDEST_ROW_BYTES} bytes, would reach 4 GiB: no kernel on "
                          f"that path has been run past 32-bit byte offsets (25 frames at 1024x576 is 3.8 GB and served)")
+    if getattr(args, "finite_guard", "off") == "fallback" and resolve_precision(args)[0] == "bfloat16":
+        raise SystemExit("--finite_guard fallback with --weight_dtype bfloat16: the fallback chain IS the bfloat16 chain, there is "
+                         "nothing to fall back to (use --finite_guard error)")
     if args.num_past_obs != 1:
         raise SystemExit(f"--num_past_obs {args.num_past_obs}: the WM-server protocol carries ONE conditioning image per candidate "
                          f"(the reference's served path asserts past_obs_pixel is None, eval_inference.py:236-242); P > 1 tokens are "

@@ -29,6 +29,7 @@ import torch
 from .config import UNetConfig
 from .hip import (A_CONV3X3, A_CONV3X3_S2, A_CONV3X3_UP, A_CONV_T3, A_DENSE, EPI_GEGLU, EPI_OUT_F32, EPI_SILU,
                   FFN_C, FFN_CHUNK, FFN_HIDDEN, GEGLU_TILE, K_CMAJOR, K_HALO32, Hip, TiledW, tile_weight)
+from .range import scoped
 from .weights import validate_state_dict
 
 CIN_PAD = 64  # conv_in input channels padded 8 -> 64 so it runs on the MFMA conv kernel
@@ -542,6 +543,7 @@ class UNetHIP:
     # ------------------------------------------------------------------------------------------
     # blocks
     # ------------------------------------------------------------------------------------------
+    @scoped()
     def _res_block(self, p, x1, C1, x2, C2, Cout, M, H, W, temb_all, eps, ncand=1):
         """SpatioTemporalResBlock (resnet.py:686-716) on token-major tensors; (x1|x2) is the channel concat.  ncand: the
         candidates in the batch (`_conv3`).  xs and the block output are block-level stream tensors (`res32_any`)."""
@@ -614,6 +616,7 @@ class UNetHIP:
         o2 = hip.cross_attn_fewkeys(q2, Cn, K, V, a2, Cn, M, rows_per_item, heads, cond.P, 1.0 / math.sqrt(64.0))
         return self._linear(o2, q + ".attn2.to_out.0", M, res1=h, out_f32=h.dtype == torch.float32)   # stays on h's stream
 
+    @scoped()
     def _transformer(self, p, x, Cn, M, H, W, heads, cond: RequestCond):
         """TransformerSpatioTemporalModel (transformer_temporal.py:279-382), one layer.  x is a block-level stream tensor
         (`res32_any`); the hidden stream between proj_in and proj_out is fp32 only with `res32_tr`."""
@@ -726,6 +729,7 @@ class UNetHIP:
         return self.hip.emb_combine(temb, cond.act_emb, cond.noise_emb, cond.Bc, cond.B, cfg.num_frames,
                                     cfg.time_embed_dim, out)
 
+    @scoped("unet")
     def forward(self, x_in: torch.Tensor, emb_silu: torch.Tensor, cond: RequestCond, h: int, w_: int) -> torch.Tensor:
         """x_in: bf16 [Bc*T*h*w, 64] (wiw_prep_unet_input); emb_silu: bf16 [Bc*T, E] (time_embedding()).
         Returns fp32 [Bc*T*h*w, 4] (token-major v-prediction)."""

@@ -28,6 +28,7 @@ import torch
 
 from .frontend import vae_state_dict_spec
 from .hip import A_CONV3X3, A_CONV3X3_S2P, A_CONV3X3_UP, A_CONV_T3, EPI_OUT_F32, Hip
+from .range import scoped, stats_records
 
 CIN_PAD = 64   # conv_in input channels (4 latent / 3 pixel) are zero-padded to one 64-wide K tile
 
@@ -161,6 +162,7 @@ class VAEHIP:
             out = self._empty(M, N)
         return self.hip.gemm(x, Wt, out, M=M, N=N, K=9 * Cin, C1=Cin, mode=mode, H=H, Wd=W, bias=self.w[p + ".bias"], **kw)
 
+    @scoped()
     def _res2d(self, p, x, Cin, M, H, W, eps=1e-6):
         """ResnetBlock2D without time embedding (resnet.py:320-373)."""
         hip, w = self.hip, self.w
@@ -178,6 +180,7 @@ class VAEHIP:
             sc = x
         return self._conv3(p + ".conv2", hn, M, Cout, H, W, res1=sc, ldr1=Cout, beta1=1.0), Cout
 
+    @scoped()
     def _st_res(self, p, x, Cin, M, H, W, T):
         """SpatioTemporalResBlock of the temporal decoder: temb None, merge 'learned', switched mix."""
         hip, w = self.hip, self.w
@@ -194,6 +197,7 @@ class VAEHIP:
                  bias=w[t + ".conv2.bias"], alpha=self.mix[p], res1=xs, ldr1=C, beta1=1.0)
         return h, C
 
+    @scoped()
     def _attn(self, p, x, C, frames, S):
         """GroupNorm -> single-head softmax(QK^T / sqrt(C)) V -> to_out + residual, per frame."""
         hip, w = self.hip, self.w
@@ -224,6 +228,7 @@ class VAEHIP:
     # decode / encode
     # ------------------------------------------------------------------------------------------
     @torch.no_grad()
+    @scoped("vae.decoder")
     def decode_frames(self, z: torch.Tensor) -> torch.Tensor:
         """z: fp32 (T, L, h, w) latents of ONE clip, already divided by scaling_factor (the reference decodes
         `decode_chunk_size = num_frames` frames per call, pipeline:291-302).  Returns fp32 (T, 3, 8h, 8w)."""
@@ -271,6 +276,7 @@ class VAEHIP:
         m = self._encode(x, "encoder.moments_conv", 2 * L)
         return m[:, :L].contiguous(), torch.clamp(m[:, L:], -30.0, 20.0).contiguous()
 
+    @scoped("vae.encoder")
     def _encode(self, x: torch.Tensor, head: str, L: int) -> torch.Tensor:
         hip, w, ch, lpb = self.hip, self.w, self.ch, self.lpb
         x = x.to(self.device, torch.float32).contiguous()
@@ -384,10 +390,28 @@ class HIPFrontend:
             return lat, emb
         return lat.cpu().numpy(), emb.cpu().numpy()
 
+    def candidate_stats(self, t: torch.Tensor) -> torch.Tensor:
+        """`Hip.range_stats` of a contiguous fp32 device tensor (B, ...), one segment per candidate: the device buffer of B
+        WiwRangeStats, not read here (`range.stats_records` after the caller's synchronisation)."""
+        assert t.dtype == torch.float32
+        t = t.contiguous()          # what the denoising loop and the decoder hand over already is
+        B = t.shape[0]
+        return self.vae.hip.range_stats(t, rows=B, cols=t.numel() // B, rows_per_segment=1, f32=True)[0]
+
     @torch.no_grad()
-    def decode(self, latents) -> np.ndarray:
+    def decode(self, latents, range_out: Optional[list] = None) -> np.ndarray:
+        """range_out (here and in `decode_uint8` / `decode_resized_uint8`): a list that receives one `range.stats_records`
+        record per candidate, in order — the NaN / inf counts and the range of the fp32 frames held here before they are
+        quantised or copied (the serving guard's second check point).  The statistics are launched behind the decoder and
+        read after the frames' own copy to the host: no synchronisation is added.  None: nothing more is launched."""
         z = latents if torch.is_tensor(latents) else torch.from_numpy(np.ascontiguousarray(latents))
-        return self.vae.decode(z).cpu().numpy()
+        if range_out is None:
+            return self.vae.decode(z).cpu().numpy()
+        frames = self.vae.decode(z)
+        st = self.candidate_stats(frames)
+        out = frames.cpu().numpy()
+        range_out.extend(stats_records(st))
+        return out
 
     @torch.no_grad()
     def decode_device(self, latents) -> torch.Tensor:
@@ -397,30 +421,38 @@ class HIPFrontend:
         return self.vae.decode(z)
 
     @torch.no_grad()
-    def decode_resized_uint8(self, latents, out_size, filter: str = "bicubic") -> np.ndarray:
+    def decode_resized_uint8(self, latents, out_size, filter: str = "bicubic", range_out: Optional[list] = None) -> np.ndarray:
         """decode + frame quantisation + PIL resize to out_size = (ow, oh), all on the device: uint8 (B, T, 3, oh, ow) on the
         host, the response's own layout.  `Hip.frames_resample_u8` quantises the fp32 frames at its loads (the arithmetic of
         `frames_to_uint8_device`) and resamples with PIL's integer tables, so the bytes are those of `decode_uint8` + `Image.resize`;
-        no (T, H, W, 3) uint8 copy is made and oh * ow * 3 * T bytes per candidate cross PCIe."""
+        no (T, H, W, 3) uint8 copy is made and oh * ow * 3 * T bytes per candidate cross PCIe.  range_out: see `decode`."""
         z = latents if torch.is_tensor(latents) else torch.from_numpy(np.ascontiguousarray(latents))
         ow, oh = out_size
         out = []
         for b in range(z.shape[0]):          # per clip: bounds the fp32 frame buffer to one candidate
             frames = self.vae.decode(z[b:b + 1])[0]
             T, Cc, H, W = frames.shape
+            st = self.candidate_stats(frames[None]) if range_out is not None else None
             u8 = self.vae.hip.frames_resample_u8(frames.reshape(T * Cc, H, W), oh, ow, filter)
             out.append(u8.reshape(T, Cc, oh, ow).cpu().numpy())
+            if st is not None:
+                range_out.extend(stats_records(st))
         return np.stack(out)
 
     @torch.no_grad()
-    def decode_uint8(self, latents: np.ndarray) -> np.ndarray:
+    def decode_uint8(self, latents: np.ndarray, range_out: Optional[list] = None) -> np.ndarray:
         """decode + the frame quantisation of `frames_to_pil` on the device: (x/2 + 0.5).clamp(0, 1) * 255, round half
         to even, uint8, HWC (image_processor.py:133-147) — the same fp32 operations in the same order, so the bytes
-        are identical; 25 MB instead of 99 MB cross PCIe per candidate and the host skips a 0.3-0.7 s numpy pass."""
+        are identical; 25 MB instead of 99 MB cross PCIe per candidate and the host skips a 0.3-0.7 s numpy pass.
+        range_out: see `decode`."""
         z = latents if torch.is_tensor(latents) else torch.from_numpy(np.ascontiguousarray(latents))
         out = []
         for b in range(z.shape[0]):          # per clip: bounds the fp32 frame buffer to one candidate
-            out.append(frames_to_uint8_device(self.vae.decode(z[b:b + 1])[0]).cpu().numpy())
+            frames = self.vae.decode(z[b:b + 1])[0]
+            st = self.candidate_stats(frames[None]) if range_out is not None else None
+            out.append(frames_to_uint8_device(frames).cpu().numpy())
+            if st is not None:
+                range_out.extend(stats_records(st))
         return np.stack(out)
 
 
